@@ -1,6 +1,7 @@
 """bench.py — concept-DB build throughput (BASELINE.json configs[1]) + text_probing, on N MI355X.
 
-    python bench.py --gpus 1 --steps 20 --warmup 3
+    python bench.py --gpus 1 --steps 20 --warmup 3        # the headline job alone
+    python bench.py --gpus 1 --steps 20 --warmup 3 --full # + strong scaling, oracle self-checks, every other leg, CPU baselines
     python bench.py --gpus 8 --steps 20 --warmup 3        # launches its own 8 ranks (one per GPU, RCCL), prints ONE line
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
@@ -55,6 +56,35 @@ def roofline_hbm(gbps, **more):
     return out
 
 
+def pin_conv_algorithms():
+    """Let MIOpen take the headline's convolution algorithms from bench_data/ instead of timing candidates in every process.
+
+    With torch.backends.cudnn.benchmark off, PyTorch still runs MIOpen's Find on a find-db miss, which times the applicable
+    solvers and keeps the fastest.  Several ResNet-50 layers have near-tied solvers (Winograd variants), so two processes with
+    empty databases pick different algorithms, the activations differ in their last bits, bf16 top-k ties resolve differently
+    and the top-k ids and concept_db rows differ from run to run.  bench_data/gfx950100.HIP.fdb.txt holds the records one Find
+    wrote for the batch-256 forward on an MI355X (gfx950, 256 CUs); served as a system find-db next to the files of torch's own
+    MIOpen database, they are hits: the same, fastest-found algorithms in every run.  Other GPUs and shapes find as before.
+    A caller's MIOPEN_SYSTEM_DB_PATH is left alone."""
+    import atexit
+    import shutil
+    import tempfile
+
+    if "MIOPEN_SYSTEM_DB_PATH" in os.environ:
+        return
+    db = Path(torch.__file__).resolve().parent / "share" / "miopen" / "db"
+    tmp = Path(tempfile.mkdtemp(prefix="sl_bench_miopen_db_"))
+    atexit.register(shutil.rmtree, tmp, True)
+    for f in (db.iterdir() if db.is_dir() else ()):
+        (tmp / f.name).symlink_to(f)
+    for rec in (ROOT / "bench_data").glob("*.fdb.txt"):
+        target = tmp / rec.name
+        text = (target.read_text() if target.exists() else "") + rec.read_text()
+        target.unlink(missing_ok=True)
+        target.write_text(text)
+    os.environ["MIOPEN_SYSTEM_DB_PATH"] = str(tmp)
+
+
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -87,8 +117,16 @@ def parse():
                     help="keep only this many distinct batches resident and cycle through them (ids stay unique); 0 = every "
                          "batch distinct.  For dataset sizes whose uint8 pixels exceed HBM (1.28 M images = 193 GB)")
     ap.add_argument("--leg-steps", type=int, default=0, help="batches of the configs[3] / configs[4] collect legs (default 8 / 4; tests: fewer)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: strong scaling, the oracle self-checks, tie modes, ceilings, sweep and every "
+                         "other leg (configs[3] / [4], fp32 GEMMs, channels_last, half precision, API path, text_probing, CPU "
+                         "baselines).  Without it a run sets up, warms up, times the headline job and prints its line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed job, write what it computed as DIR/<name>.npy (float32 / float64, under 48 MiB): per layer "
+                         "the top-k activations and sample ids of every component and the concept_db rows of a fixed, seeded "
+                         "sample of the components (bench_outputs/ is git-ignored)")
     ap.add_argument("--no-self-check", action="store_true")
-    ap.add_argument("--quick", action="store_true", help="headline + self-check only: none of the extra legs (tests)")
+    ap.add_argument("--quick", action="store_true", help="with --full: headline + self-check only, none of the extra legs (tests)")
     ap.add_argument("--no-tokens-leg", action="store_true", help="skip the configs[3] leg (ViT-B/16 collect + so400m embed + 10k-prompt probing)")
     ap.add_argument("--no-config4-leg", action="store_true", help="skip the configs[4] leg (ConvNeXt-L collect + relevance visualizer + scores)")
     ap.add_argument("--no-half-leg", action="store_true")
@@ -196,6 +234,33 @@ def finish_job(cv, embeds, id_start, n_total, sharded):
         return {n: sld.gather_concept_db_sharded(embeds, id_start, n_total, cv.get_max_reference(n)) for n in cv.layer_names}
     # one K5 launch over the ids of all layers (what `_compute_concept_db` runs), straight from the device-resident states
     return cv._gather_layers(embeds, {n: cv.actmax_cache.cache[n].device_state()[1] for n in cv.layer_names}, True)
+
+
+DUMP_BYTES = 48 << 20  # --dump-outputs: the whole concept_db is C * k * 512 * 4 bytes (147 MB for layer2-4 at k = 20)
+
+
+@torch.no_grad()
+def dump_outputs(out_dir, cv, concept_db):
+    """What a caller of the timed job receives, as ``out_dir/<name>.npy``: per layer the top-k activations (bf16, exact in float32)
+    and sample ids (float64) of every component, and ``concept_db`` (float32) for a fixed, seeded sample of the components, whose
+    indices are stored beside it.  The sample depends on the layer widths and k only, so the same arguments dump the same rows."""
+    import numpy as np
+
+    arrays = {}
+    for name in cv.layer_names:
+        am = cv.actmax_cache.cache[name]
+        arrays[f"topk_activations_{name}"] = am.activations.float().numpy()
+        arrays[f"topk_sample_ids_{name}"] = am.sample_ids.numpy().astype(np.float64)
+    per_layer = (DUMP_BYTES - sum(a.nbytes for a in arrays.values())) // len(concept_db)
+    rng = np.random.default_rng(0)
+    for name, db in concept_db.items():
+        row_bytes = db[0].numel() * 4 + 8  # the rows and their index
+        comps = np.sort(rng.choice(db.shape[0], size=min(db.shape[0], per_layer // row_bytes), replace=False))
+        arrays[f"concept_db_{name}"] = db[torch.from_numpy(comps).to(db.device)].float().cpu().numpy()
+        arrays[f"concept_db_{name}_components"] = comps.astype(np.float64)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    for key, a in arrays.items():
+        np.save(out_dir / f"{key}.npy", a)
 
 
 @torch.no_grad()
@@ -359,6 +424,32 @@ def api_path_leg(dev, model, fm_base, args):
                         "(K12), tie_mode='aten', concept_db returned on the host"}
 
 
+def usable_cores() -> int:
+    """The CPUs this process may use: its affinity mask, capped by a cgroup CPU quota and by OMP_NUM_THREADS when either is set.
+    One thread per logical CPU of a box that gives the process a far smaller share ran the CPU job 1000x slower than 32 threads
+    (profiles/r06_bench_line.json: 0.028 images/s on 256 threads)."""
+    try:
+        n = len(os.sched_getaffinity(0))
+    except AttributeError:
+        n = os.cpu_count() or torch.get_num_threads()
+    quotas = []
+    try:
+        rel = next((ln[3:] for ln in Path("/proc/self/cgroup").read_text().splitlines() if ln.startswith("0::")), "/")
+        d = Path("/sys/fs/cgroup" + rel)
+        for f in [p / "cpu.max" for p in (d, *d.parents) if p.is_relative_to("/sys/fs/cgroup")]:  # cgroup v2, up to the root
+            if f.is_file() and f.read_text().split()[0] != "max":
+                quota, period = f.read_text().split()[:2]
+                quotas.append(int(quota) / int(period))
+        v1 = Path("/sys/fs/cgroup/cpu")  # cgroup v1
+        if (v1 / "cpu.cfs_quota_us").is_file() and int((v1 / "cpu.cfs_quota_us").read_text()) > 0:
+            quotas.append(int((v1 / "cpu.cfs_quota_us").read_text()) / int((v1 / "cpu.cfs_period_us").read_text()))
+    except (OSError, ValueError):
+        pass
+    if os.environ.get("OMP_NUM_THREADS", "").isdigit() and int(os.environ["OMP_NUM_THREADS"]) > 0:
+        quotas.append(int(os.environ["OMP_NUM_THREADS"]))
+    return max(1, min([n] + [int(q) for q in quotas]))
+
+
 def cpu_baseline(args, model_cpu, fm_cpu):
     """The CPU path (oracle = port of the reference's arithmetic) on a bounded sample of the same
     workload, on this box's host cores: torch-CPU forward under hooks -> oracle aggregate ->
@@ -372,12 +463,10 @@ def cpu_baseline(args, model_cpu, fm_cpu):
     # sustains: on the MI355X boxes 8-32 threads beat 256 by 20-70x) for ONE BATCH'S COMPUTE of the job — ResNet-50 forward + CLIP
     # encode of 32 images after an 8-image call of both (the forward alone picked 2 threads on one box of round 6: 32 images/s for
     # the forward, 10 for the job).  Counts past the first one that falls below half of the best are not probed (a 64-image forward
-    # with one thread per logical CPU of a 256-CPU box costs minutes); all cores get a 4-image probe in that case.
+    # with one thread per logical CPU of a 256-CPU box costs minutes); all cores get a 4-image probe in that case.  "All cores" are
+    # the ones this process may use (usable_cores: the affinity mask under the cgroup quota and OMP_NUM_THREADS).
     probe_u8 = synth.synth_images_u8(torch.arange(10**7, 10**7 + 32))
-    try:
-        all_cores = len(os.sched_getaffinity(0))
-    except AttributeError:
-        all_cores = os.cpu_count() or torch.get_num_threads()
+    all_cores = usable_cores()
     best_t, best_rate = torch.get_num_threads(), 0.0
     cands = sorted({t for t in (2, 4, 8, 16, 32, 64, 128, all_cores) if t <= all_cores})
     thread_probe = {}
@@ -973,10 +1062,7 @@ def cpu_baseline_scores(threads_best: int):
 
     import oracle  # checker / baseline only
 
-    try:
-        all_cores = len(os.sched_getaffinity(0))
-    except AttributeError:
-        all_cores = os.cpu_count()
+    all_cores = usable_cores()
     g = torch.Generator().manual_seed(6)
     x, y = torch.randn(10000, 1152, generator=g), torch.randn(768, 1152, generator=g)
     V = torch.randn(2048, 20, 512, generator=g)
@@ -991,7 +1077,7 @@ def cpu_baseline_scores(threads_best: int):
             ts.append(time.perf_counter() - t)
         return min(ts)
 
-    out = {"kind": "port", "threads_best": threads_best, "host_cores_affinity": all_cores,
+    out = {"kind": "port", "threads_best": threads_best, "usable_cores": all_cores,
            "sample": "similarity (10000,1152)x(768,1152)^T = one configs[3] layer (7.68 M similarities); clarity (2048,20,512); "
                      "polysemanticity 64 x (20,512) through scikit-learn; best of 3 after one warm-up call"}
     before = torch.get_num_threads()
@@ -1109,10 +1195,13 @@ class _quiet_stdout:
 
 def self_launch(args):
     """`python bench.py --gpus N` outside torch.distributed.run: start the N ranks ourselves — one process per GPU, backend
-    nccl (= RCCL) — by re-executing this file under torch.distributed.run on a free local port.  Rank 0 prints the ONE JSON
-    line.  A box with fewer than N GPUs is refused loudly (SL_BENCH_SHARE_GPU=1: N ranks on GPU 0 over gloo — a debugging /
-    test aid for the N > 1 code path, never a measurement)."""
+    nccl (= RCCL) — by running this file under torch.distributed.run on a free local port, in a child process (this one has
+    asked the runtime for its devices already); its exit status is ours.  Rank 0 prints the ONE JSON line.  A box with fewer
+    than N GPUs is refused loudly (SL_BENCH_SHARE_GPU=1: N ranks on GPU 0 over gloo — a debugging / test aid for the N > 1
+    code path, never a measurement)."""
+    import signal
     import socket
+    import subprocess
 
     have = torch.cuda.device_count()
     env = dict(os.environ)
@@ -1129,13 +1218,16 @@ def self_launch(args):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}", "--master-addr", "127.0.0.1",
            "--master-port", str(port), str(Path(__file__).resolve())] + sys.argv[1:]
     sys.stdout.flush()
-    os.execvpe(sys.executable, cmd, env)
+    child = subprocess.Popen(cmd, env=env)
+    signal.signal(signal.SIGTERM, lambda signum, frame: child.send_signal(signum))  # a stop for this process stops the ranks
+    raise SystemExit(child.wait())
 
 
 def main():
     args = parse()
+    pin_conv_algorithms()  # before the first convolution of this process
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
-        self_launch(args)  # does not return
+        self_launch(args)  # exits with the ranks' status
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -1183,6 +1275,8 @@ def main():
     torch.backends.cudnn.benchmark = bool(args.miopen_find)
     global OVERLAP
     OVERLAP = bool(args.overlap)
+    if not args.full:  # a plain run is the headline job alone: no oracle check and no other leg
+        args.quick = args.no_self_check = True
     if args.quick:
         args.no_api_leg = args.no_channels_last = args.no_probing = args.no_cpu_baseline = True
         args.no_tokens_leg = args.no_half_leg = args.no_config4_leg = True
@@ -1277,6 +1371,8 @@ def main():
     N.prof_enable(False)
     elapsed = all_max(elapsed)
     assert all(v.shape == (c, args.k, 512) for v, c in zip(concept_db.values(), (512, 1024, 2048)))
+    if args.dump_outputs and rank == 0:
+        dump_outputs(Path(args.dump_outputs), last_cv[0], concept_db)
     del concept_db
 
     # ---- strong scaling: the north star's 1.28 M-image set in TOTAL, sharded over the ranks (every rank takes part) ----

@@ -35,7 +35,7 @@ only gradient x activation:
 """
 from __future__ import annotations
 
-from contextlib import contextmanager
+from contextlib import contextmanager, nullcontext
 
 import torch
 from torch import nn
@@ -104,7 +104,11 @@ class _LinearRule(torch.autograd.Function):
             passes = [(torch.ones_like(a), torch.ones_like(w), None)]
         else:
             raise ValueError(rule)
-        with torch.enable_grad():
+        # on the host the rule's convolutions and their input gradients run on ATen's own kernels: oneDNN picks its backward-data
+        # kernel per machine (ISA, caches, cores), and one such pick returned wrong relevance for the test network of tests/test_lrp.py
+        # (forward and logits bit-equal to other hosts); the device path is unaffected
+        host = torch.backends.mkldnn.flags(False, None, None, None) if a.device.type == "cpu" else nullcontext()  # only `enabled`
+        with torch.enable_grad(), host:
             ins = [p[0].requires_grad_(True) for p in passes]
             z = sum(f(x, pw, pb) for x, (_, pw, pb) in zip(ins, passes))
             s = (r_out / _stabilise(z, eps)).detach()

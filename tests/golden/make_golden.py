@@ -35,7 +35,7 @@ from helpers import (  # noqa: E402
 from semanticlens import scores as ref_scores  # noqa: E402
 from semanticlens.component_visualization import aggregators as ref_agg  # noqa: E402
 from semanticlens.component_visualization.activation_based import ActivationComponentVisualizer  # noqa: E402
-from semanticlens.component_visualization.activation_caching import ActMax  # noqa: E402
+from semanticlens.component_visualization.activation_caching import ActMax, ActMaxCache  # noqa: E402
 from semanticlens.lens import Lens, _embed_text_probes, image_probing  # noqa: E402
 
 
@@ -310,6 +310,29 @@ def gen_image_probes():
     save("image_probes", **out)
 
 
+def gen_cache_interchange():
+    """activation_caching.py:434-465 — the files the reference's ActMaxCache.store writes for two layers' top-k states (bf16
+    activations, int64 ids incl. -1): file names, safetensors header and payload, stored byte for byte next to the states."""
+    g = torch.Generator().manual_seed(43)
+    cache = ActMaxCache(["layer4", "fc"], ref_agg.aggregate_conv_max, 5)
+    out = {}
+    for i, name in enumerate(("layer4", "fc")):
+        am = ActMax(n_collect=5, n_latents=6)
+        am._setup_tensors()
+        am.activations = (torch.rand(6, 5, generator=g) + i).to(torch.bfloat16)
+        am.sample_ids = torch.randint(-1, 1000, (6, 5), generator=g)
+        cache.cache[name] = am
+        out[f"act_{name}"] = bf16_bits(am.activations)
+        out[f"ids_{name}"] = am.sample_ids.numpy()
+    with tempfile.TemporaryDirectory() as d:
+        cache.store(d)
+        files = sorted(Path(d).iterdir())
+        out["file_names"] = np.array([f.name for f in files])
+        for i, f in enumerate(files):
+            out[f"file_{i}"] = np.frombuffer(f.read_bytes(), dtype=np.uint8)
+    save("cache_interchange", **out)
+
+
 def gen_scores_k():
     """polysemanticity_score(n_clusters=k) of the reference for k != 2 (scores.py:132,167): random rows, three / four
     well-separated blobs, rows with duplicated points (empty clusters, the < 2 samples fallback)."""
@@ -370,6 +393,7 @@ GENERATORS = {
     "text_probes": gen_text_probes,
     "pipeline": gen_pipeline,
     "image_probes": gen_image_probes,
+    "cache_interchange": gen_cache_interchange,
 }
 
 if __name__ == "__main__":

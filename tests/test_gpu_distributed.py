@@ -135,7 +135,7 @@ def _bench_line(extra_env, args, nproc):
     return json.loads(lines[0])
 
 
-BUILD_ONLY = ["--no-tokens-leg", "--no-config4-leg", "--no-probing", "--no-cpu-baseline"]  # the headline job (+ strong scaling) alone
+BUILD_ONLY = ["--no-tokens-leg", "--no-config4-leg", "--no-probing", "--no-cpu-baseline"]  # with --full: the headline job + strong scaling
 
 
 def test_bench_two_ranks_sharing_one_gpu_over_gloo():
@@ -144,7 +144,7 @@ def test_bench_two_ranks_sharing_one_gpu_over_gloo():
     configs[3] / configs[4] collect legs with the cross-rank merge, text_probing with the query rows sharded, the scores with the
     component axis sharded, the CPU baseline (rank 0) and the oracle / single-process parity of each."""
     line = _bench_line({"SL_BENCH_BACKEND": "gloo", "SL_BENCH_SHARE_GPU": "1"}, ["--steps", "3", "--batches-per-step", "2", "--warmup", "1", "--batch", "64", "--min-warmup-seconds", "0.3",
-                                                                                 "--strong-images", "1500", "--strong-pool-batches", "4", "--cpu-images", "64", "--leg-steps", "2"], 2)
+                                                                                 "--strong-images", "1500", "--strong-pool-batches", "4", "--cpu-images", "64", "--leg-steps", "2", "--full"], 2)
     assert line["strong_scaling"]["images"] == 1500 and line["strong_scaling"]["tie_mode"] == "total"  # (the default is the 1.28 M-image job: 200 s here)
     assert line["n_gpus"] == 2 and line["steps"] == 3 and line["scaling"] == "weak"
     assert line["config"]["images_total"] == 2 * 3 * 2 * 64 and line["value"] > 0
@@ -359,7 +359,7 @@ def test_bench_distributed_path_over_rccl_on_one_gpu():
     """`bench.py` with SL_BENCH_FORCE_DIST=1: a one-rank nccl group, so the N > 1 code of the bench (barriers, packed all-gather,
     K4 merge, sharded K5 + all-reduce, max-over-ranks timing) runs over RCCL on the 1-GPU box."""
     line = _bench_line({"SL_BENCH_FORCE_DIST": "1"}, ["--steps", "2", "--batches-per-step", "2", "--warmup", "1", "--batch", "64",
-                                                        "--min-warmup-seconds", "0.3", "--quick"], 1)
+                                                        "--min-warmup-seconds", "0.3", "--quick", "--full"], 1)
     assert line["n_gpus"] == 1 and line["config"]["collectives"].startswith("libsemanticlens_hip.so (RCCL behind the C ABI)")
     assert line["config"]["rccl_world_size"] == 1 and line["config"]["tie_mode"] == "total"
     assert all(line["sharded_check"][k_] for k_ in ("topk_values_equal", "topk_ids_equal", "concept_db_equal"))
@@ -381,7 +381,7 @@ def test_bench_launches_its_own_ranks():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env["SL_BENCH_SHARE_GPU"] = "1"
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--batches-per-step", "2", "--warmup", "1",
-           "--batch", "64", "--min-warmup-seconds", "0.2", "--strong-images", "333", "--strong-pool-batches", "2"] + BUILD_ONLY
+           "--batch", "64", "--min-warmup-seconds", "0.2", "--strong-images", "333", "--strong-pool-batches", "2", "--full"] + BUILD_ONLY
     res = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900, cwd=root)
     assert res.returncode == 0, res.stderr[-3000:]
     lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]

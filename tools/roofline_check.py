@@ -9,8 +9,8 @@ difference of the two per-dispatch averages = what attaching the tool changes, m
 Inputs under <dir>/ (tools/run_profiles_r03.sh):
   <R>_k1_cold_kernel_stats.csv           trace of tools/k1_cold_target.py         | <R>_k1_cold_events.json (no tool)
   <R>_reduce_pipe1_kernel_stats.csv      trace of tools/native/reduce_lab pipe1   | <R>_reduce_pipe1_lab.log (no tool)
-  <R>_k1_inpipeline1s_kernel_stats.csv   trace of bench.py --quick --no-overlap   | <R>_bench_line_quick1s.json (no tool)
-  <R>_k1_inpipeline_kernel_stats.csv     trace of bench.py --quick (two streams)  | <R>_bench_line_quick.json (no tool)
+  <R>_k1_inpipeline1s_kernel_stats.csv   trace of bench.py --full --quick --no-overlap | <R>_bench_line_quick1s.json (no tool)
+  <R>_k1_inpipeline_kernel_stats.csv     trace of bench.py --full --quick (two streams) | <R>_bench_line_quick.json (no tool)
 """
 import csv
 import json
@@ -75,7 +75,7 @@ def main(d, R):
             ref = {la: SHAPES[la] / (float(g) * 1e9) * 1e6 for la, g in zip(LAYERS, m.groups())}
         section("in-pipeline, native harness (tools/native/reduce_lab pipe1: in-place ReLU over the input, then K1, one stream, shipped policy)",
                 k1_rows(f("reduce_pipe1_kernel_stats.csv")), ref)
-    for tag, name in (("one stream (bench.py --quick --no-overlap)", "1s"), ("two streams, the headline's condition (bench.py --quick)", "")):
+    for tag, name in (("one stream (bench.py --full --quick --no-overlap)", "1s"), ("two streams, the headline's condition (bench.py --full --quick)", "")):
         csvp = f(f"k1_inpipeline{name}_kernel_stats.csv")
         if not os.path.exists(csvp):
             continue

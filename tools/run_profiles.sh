@@ -6,8 +6,8 @@ set -u
 R=${1:-r02}
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 O=gpurun_out
-python bench.py --steps 20 --warmup 3 > $O/${R}_bench_line.json 2> $O/${R}_bench_line.err
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_trace -- python bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-api-leg > $O/${R}_bench_line_profiled.json 2> $O/prof_trace.err
+python bench.py --steps 20 --warmup 3 --full > $O/${R}_bench_line.json 2> $O/${R}_bench_line.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_trace -- python bench.py --steps 20 --warmup 3 --full --no-cpu-baseline --no-api-leg > $O/${R}_bench_line_profiled.json 2> $O/prof_trace.err
 python tools/prof_summarize.py trace $O/prof_trace $O/${R}_bench_kernel_stats.csv
 rm -rf $O/prof_trace
 pmc() {  # name target counters...

@@ -2,7 +2,7 @@
 # Round-3 measurement artefacts under gpurun_out/ (copy the summaries into profiles/).  One counter group per --pmc run,
 # never combined with a trace domain other than the kernel trace (MI355X_MICROARCH.md).
 #   K1 is traced per REGIME, in separate processes, so that bytes / AverageNs of a CSV row is one regime's number:
-#     bench.py --quick            -> in-pipeline launches only (warm-up + timed job + self-check)
+#     bench.py --full --quick     -> in-pipeline launches only (warm-up + timed job + self-check)
 #     tools/k1_cold_target.py     -> cold launches only
 #   each also run WITHOUT the tool: the difference of the HIP-event averages is the tool's per-dispatch overhead.
 set -u
@@ -16,13 +16,13 @@ trace() {  # name command...
   python tools/prof_summarize.py trace $O/prof_trace $O/${R}_${name}_kernel_stats.csv
   rm -rf $O/prof_trace
 }
-python bench.py --steps 20 --warmup 3 > $O/${R}_bench_line.json 2> $O/${R}_bench_line.err
-python bench.py --steps 20 --warmup 3 --quick > $O/${R}_bench_line_quick.json 2>> $O/${R}_bench_line.err
-trace k1_inpipeline python bench.py --steps 20 --warmup 3 --quick
+python bench.py --steps 20 --warmup 3 --full > $O/${R}_bench_line.json 2> $O/${R}_bench_line.err
+python bench.py --steps 20 --warmup 3 --full --quick > $O/${R}_bench_line_quick.json 2>> $O/${R}_bench_line.err
+trace k1_inpipeline python bench.py --steps 20 --warmup 3 --full --quick
 mv $O/${R}_k1_inpipeline.stdout $O/${R}_bench_line_quick_profiled.json
 # one stream (no encoder beside K1): the tool's host-side launch cost cannot shift the overlap of two streams
-python bench.py --steps 20 --warmup 3 --quick --no-overlap > $O/${R}_bench_line_quick1s.json 2>> $O/${R}_bench_line.err
-trace k1_inpipeline1s python bench.py --steps 20 --warmup 3 --quick --no-overlap
+python bench.py --steps 20 --warmup 3 --full --quick --no-overlap > $O/${R}_bench_line_quick1s.json 2>> $O/${R}_bench_line.err
+trace k1_inpipeline1s python bench.py --steps 20 --warmup 3 --full --quick --no-overlap
 mv $O/${R}_k1_inpipeline1s.stdout $O/${R}_bench_line_quick1s_profiled.json
 python tools/k1_cold_target.py > $O/${R}_k1_cold_events.json 2>> $O/${R}_bench_line.err
 trace k1_cold python tools/k1_cold_target.py

@@ -19,12 +19,12 @@ pmc() {  # name target counters...
   python tools/prof_summarize.py pmc $O/prof_pmc $O/${R}_pmc_${name}.csv
   rm -rf $O/prof_pmc
 }
-python bench.py --steps 20 --warmup 5 > $O/${R}_bench_line.json 2> $O/${R}_bench_line.err
-python bench.py --steps 20 --warmup 5 --quick > $O/${R}_bench_line_quick.json 2>> $O/${R}_bench_line.err
-trace k1_inpipeline python bench.py --steps 20 --warmup 5 --quick
+python bench.py --steps 20 --warmup 5 --full > $O/${R}_bench_line.json 2> $O/${R}_bench_line.err
+python bench.py --steps 20 --warmup 5 --full --quick > $O/${R}_bench_line_quick.json 2>> $O/${R}_bench_line.err
+trace k1_inpipeline python bench.py --steps 20 --warmup 5 --full --quick
 mv $O/${R}_k1_inpipeline.stdout $O/${R}_bench_line_quick_profiled.json
-python bench.py --steps 20 --warmup 5 --quick --no-overlap > $O/${R}_bench_line_quick1s.json 2>> $O/${R}_bench_line.err
-trace k1_inpipeline1s python bench.py --steps 20 --warmup 5 --quick --no-overlap
+python bench.py --steps 20 --warmup 5 --full --quick --no-overlap > $O/${R}_bench_line_quick1s.json 2>> $O/${R}_bench_line.err
+trace k1_inpipeline1s python bench.py --steps 20 --warmup 5 --full --quick --no-overlap
 mv $O/${R}_k1_inpipeline1s.stdout $O/${R}_bench_line_quick1s_profiled.json
 python tools/k1_cold_target.py > $O/${R}_k1_cold_events.json 2>> $O/${R}_bench_line.err
 trace k1_cold python tools/k1_cold_target.py

@@ -21,11 +21,11 @@ pmc() {  # name target counters...
 }
 for S in $STAGES; do case $S in
 bench)
-  python bench.py --steps 20 --warmup 5 > $O/${R}_bench_line.json 2> $O/${R}_bench_line.err
-  python bench.py --steps 20 --warmup 5 --quick > $O/${R}_bench_line_quick.json 2>> $O/${R}_bench_line.err
+  python bench.py --steps 20 --warmup 5 --full > $O/${R}_bench_line.json 2> $O/${R}_bench_line.err
+  python bench.py --steps 20 --warmup 5 --full --quick > $O/${R}_bench_line_quick.json 2>> $O/${R}_bench_line.err
   ;;
 trace)
-  trace k1_inpipeline python bench.py --steps 20 --warmup 5 --quick
+  trace k1_inpipeline python bench.py --steps 20 --warmup 5 --full --quick
   mv $O/${R}_k1_inpipeline.stdout $O/${R}_bench_line_quick_profiled.json
   # which part of the quick run launches MIOpen's naive convolution kernel
   python tools/prof_summarize.py context $O/prof_trace $O/${R}_naive_conv_context.txt naive_conv
