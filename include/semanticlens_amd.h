@@ -365,6 +365,37 @@ int sl_preprocess(const uint8_t* d_pixels, const int64_t* d_plan, int64_t B, int
                   int64_t coef_bytes, const float* h_mean, const float* h_std, float* d_out, uint8_t* d_out_u8,
                   void* d_ws, size_t ws_bytes, void* stream);
 
+/* ---- K13: concept-conditional heatmaps and rendered reference crops ------------
+ * sl_render_heatmaps replaces the per-image host loop of the reference's three plot functions
+ * (utils/render.py:13-33 _get_square_crop_box, :36-143 vis_lighten_img_border, :146-222 vis_opaque_img_border,
+ * :225-267 mystroke, :270-341 crop_and_mask_images): heat = d_rel.sum(1) (crp's attr.heatmap), torchvision
+ * gaussian_blur(kernel_size, sigma 0.15 k + 0.35, reflect padding) as two separable fp32 passes, |b| / max|b|
+ * (+1e-8 for OPAQUE / LIGHTEN), crp's get_crop_range(crop_th) + the square box, the crop decision, the composite,
+ * min-max imgify to uint8 and (OPAQUE / LIGHTEN) the one-pixel stroke and Pillow pastes.  Exact rules: DESIGN.md §K13.
+ * d_rel (B,Cin,H,W) and d_img (B,3,H,W) contiguous fp32 (d_img already in display space).  Writes d_heat (B,H,W) the
+ * normalised blurred heat (may be NULL), d_box (B,4) int32 {row1, row2, col1, col2} — the square box as computed, ends
+ * exclusive and possibly past H / W (slicing clamps) —, d_flags (B) int32 bit 0 = the crop was applied, bit 1 = the
+ * rendered mask is non-empty, d_rgb (B,H,W,3) uint8 canvas with the rendered image at its top-left (its extent: the
+ * clamped box when bit 0 is set, else H x W).  d_ws: sl_render_ws_bytes(B, H, W) bytes.
+ * Refused before any launch: kernel_size even or kernel_size // 2 >= H or W (torch's reflect pad), alpha outside
+ * [0, 1], vis_th / crop_th outside [0, 1) (the reference's ValueError texts); kernel_size > 255 or
+ * W + kernel_size - 1 > 16384 is SL_E_UNSUPPORTED. */
+#define SL_RENDER_CROP 0    /* crop_and_mask_images (:270-341): always cropped, no composite */
+#define SL_RENDER_OPAQUE 1  /* vis_opaque_img_border (:146-222) */
+#define SL_RENDER_LIGHTEN 2 /* vis_lighten_img_border (:36-143) */
+size_t sl_render_ws_bytes(int64_t B, int64_t H, int64_t W);
+int sl_render_heatmaps(const float* d_rel, int64_t B, int64_t Cin, int64_t H, int64_t W, const float* d_img, int kernel_size,
+                       float vis_th, float crop_th, double alpha, int style, int rf, float* d_heat, int32_t* d_box,
+                       int32_t* d_flags, uint8_t* d_rgb, void* d_ws, size_t ws_bytes, void* stream);
+/* Start relevance of a conditional backward (zennit-crp CondAttribution with a channel condition, behind the reference's
+ * get_max_reference, component_visualization/relevance_based.py:203-246): d_act (B,C,S) strided fp32 (conv (B,C,H,W):
+ * S = H*W; tokens (B,T,F): the (B,F,T) view), d_channels (B) int64 device, one channel per row.  rf != 0: d_out = 0
+ * except d_out[i, c_i, p_i] = act[i, c_i, p_i] with p_i the FIRST argmax over S (torch.argmax: NaN largest); rf == 0:
+ * d_out[i, c_i, :] = act[i, c_i, :], zero elsewhere.  d_out (B,C,S) strided, written in one pass.  A channel outside
+ * [0, C) leaves its row zero (callers validate). */
+int sl_condition_init(const float* d_act, int64_t B, int64_t C, int64_t S, int64_t sb, int64_t sc, int64_t ss,
+                      const int64_t* d_channels, int rf, float* d_out, int64_t ob, int64_t oc, int64_t os, void* stream);
+
 /* ---- measurement --------------------------------------------------------------------------
  * When enabled, every launch of a profiled kernel family is bracketed by HIP events on its
  * own stream.  sl_prof_read synchronises those events and returns the totals. */

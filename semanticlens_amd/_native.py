@@ -28,6 +28,8 @@ TIE_MODES = {"total": SL_TIES_TOTAL, "aten": SL_TIES_ATEN}
 SL_PP_PLAN_STRIDE = 16
 PP_RESIZE_MODES = {"shortest": 0, "squash": 1}
 PP_INTERP = {"bicubic": 0, "bilinear": 1}
+SL_RENDER_CROP, SL_RENDER_OPAQUE, SL_RENDER_LIGHTEN = 0, 1, 2
+RENDER_STYLES = {"crop": SL_RENDER_CROP, "opaque": SL_RENDER_OPAQUE, "lighten": SL_RENDER_LIGHTEN}
 
 _DTYPES = {torch.float32: SL_F32, torch.float16: SL_F16, torch.bfloat16: SL_BF16}
 
@@ -100,6 +102,10 @@ SIGNATURES = {
     "sl_embed_tokens": (_int, [_vp, _i64, _vp, _i64, _i64, _i64, _vp, _vp, _vp]),
     "sl_preprocess_plan": (_int, [_vp, _vp, _i64, _int, _int, _int, _vp, _vp]),
     "sl_preprocess": (_int, [_vp, _vp, _i64, _int, _int, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "sl_render_ws_bytes": (_sz, [_i64, _i64, _i64]),
+    "sl_render_heatmaps": (_int, [_vp, _i64, _i64, _i64, _i64, _vp, _int, ctypes.c_float, ctypes.c_float, ctypes.c_double, _int, _int,
+                                  _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "sl_condition_init": (_int, [_vp, _i64, _i64, _i64, _i64, _i64, _i64, _vp, _int, _vp, _i64, _i64, _i64, _vp]),
     "sl_prof_enable": (_int, [_int]),
     "sl_prof_reset": (_int, []),
     "sl_prof_read": (_int, [_int, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(_i64), ctypes.POINTER(ctypes.c_double)]),
@@ -1094,3 +1100,76 @@ def preprocess(pixels: torch.Tensor, plan: torch.Tensor, info: dict, size: int, 
                                    ctypes.cast(m, _vp), ctypes.cast(sd, _vp), _ptr(out), _ptr(out_u8), _ptr(ws),
                                    info["ws_bytes"], _stream(pixels)), "sl_preprocess")
     return out, out_u8
+
+
+# ------------------------------------------------------------------------------------------------
+# K13: heatmap rendering (utils/render.py of the reference loops over the images on the host) and the start relevance
+# of a conditional backward
+# ------------------------------------------------------------------------------------------------
+def render_heatmaps(rel: torch.Tensor, img: torch.Tensor, style: str, kernel_size: int = 51, vis_th: float = 0.02,
+                    crop_th: float = 0.01, alpha: float = 0.4, rf: bool = False, want_heat: bool = False):
+    """K13 on ``rel`` (B, Cin, H, W) and ``img`` (B, 3, H, W) fp32 device tensors (same device) ->
+    ``(heat (B, H, W) fp32 or None, box (B, 4) int32, flags (B,) int32, rgb (B, H, W, 3) uint8)``, all on the device.
+    ``box`` is the square crop box (row1, row2, col1, col2), ``flags`` bit 0 = crop applied, bit 1 = mask non-empty; the
+    rendered image is ``rgb[b, :h, :w]`` with ``(h, w)`` the box clamped to the image when bit 0 is set, else (H, W)."""
+    if rel.ndim != 4 or img.ndim != 4 or img.shape[1] != 3 or rel.shape[0] != img.shape[0] or rel.shape[2:] != img.shape[2:]:
+        raise ValueError(f"render_heatmaps: expected rel (B, Cin, H, W) and img (B, 3, H, W), got {tuple(rel.shape)} and {tuple(img.shape)}")
+    if style not in RENDER_STYLES:
+        raise ValueError(f"render_heatmaps: style must be one of {sorted(RENDER_STYLES)}, got {style!r}")
+    _need_f32("render_heatmaps", rel, img)
+    if rel.device != img.device:
+        raise ValueError(f"render_heatmaps: rel on {rel.device}, img on {img.device}")
+    rel, img = rel.contiguous(), img.contiguous()
+    B, Cin, H, W = rel.shape
+    dev = rel.device
+    heat = torch.empty((B, H, W), dtype=torch.float32, device=dev) if want_heat else None
+    box = torch.empty((B, 4), dtype=torch.int32, device=dev)
+    flags = torch.empty((B,), dtype=torch.int32, device=dev)
+    rgb = torch.zeros((B, H, W, 3), dtype=torch.uint8, device=dev)
+    if B == 0:
+        return heat, box, flags, rgb
+    ws_bytes = lib().sl_render_ws_bytes(B, H, W)
+    ws = torch.empty((max(ws_bytes, 16),), dtype=torch.uint8, device=dev)
+    with _on(dev):
+        _check(lib().sl_render_heatmaps(_ptr(rel), B, Cin, H, W, _ptr(img), int(kernel_size), float(vis_th), float(crop_th), float(alpha),
+                                        RENDER_STYLES[style], int(bool(rf)), _ptr(heat), _ptr(box), _ptr(flags), _ptr(rgb),
+                                        _ptr(ws), ws_bytes, _stream(rel)), "sl_render_heatmaps")
+    return heat, box, flags, rgb
+
+
+def condition_init(act: torch.Tensor, channels, rf: bool) -> torch.Tensor:
+    """``grad_outputs`` of a conditional backward from the hooked layer output ``act`` ((B, C, H, W), (B, T, F) with the
+    channels on F, or (B, C)): ``rf`` keeps ``act`` at the first argmax position of channel ``channels[i]`` of row ``i``
+    only, else the whole channel; zero elsewhere.  Same shape and dtype as ``act``."""
+    if not act.is_cuda:
+        raise TypeError(f"condition_init: expected a tensor on a HIP device, got {act.device}")
+    x = act.detach()
+    if x.dtype != torch.float32:
+        x = x.float()
+    ch = torch.as_tensor(channels, dtype=torch.int64).reshape(-1)
+    if ch.numel() != x.shape[0]:
+        raise ValueError(f"condition_init: {ch.numel()} channels for {x.shape[0]} rows")
+    out = torch.zeros(x.shape, dtype=torch.float32, device=x.device)
+    if x.shape[0] == 0 or out.numel() == 0:
+        return out.to(act.dtype)
+    if x.ndim == 4:
+        B, C, H, W = x.shape
+        x, sb, sc, ss = _flatten_spatial(x)
+        S, ob, oc, os_ = H * W, C * H * W, H * W, 1
+    elif x.ndim == 3:  # tokens (B, T, F): the (B, F, T) view
+        B, T, C = x.shape
+        sb, ss, sc = x.stride()
+        S, ob, oc, os_ = T, T * C, 1, C
+    elif x.ndim == 2:
+        B, C = x.shape
+        sb, sc = x.stride()
+        S, ss, ob, oc, os_ = 1, 1, C, 1, 1
+    else:
+        raise ValueError(f"condition_init: layer outputs must be 2-, 3- or 4-D, got {x.ndim}-D")
+    if ch.numel() and (int(ch.min()) < 0 or int(ch.max()) >= C):
+        raise ValueError(f"condition_init: channel ids must lie in [0, {C}), got {ch.tolist()}")
+    ch_d = ch.to(x.device)
+    with _on(x.device):
+        _check(lib().sl_condition_init(_ptr(x), B, C, S, sb, sc, ss, _ptr(ch_d), int(bool(rf)), _ptr(out), ob, oc, os_, _stream(x)),
+               "sl_condition_init")
+    return out if act.dtype == torch.float32 else out.to(act.dtype)

@@ -243,3 +243,45 @@ def lrp_epsilon_plus_flat(model: nn.Module, layers: dict[str, nn.Module], images
         rel = by_name.get(name)
         out[name] = (act.detach(), (rel if rel is not None else torch.zeros_like(act)).detach())
     return out
+
+
+def conditional_input_relevance(model: nn.Module, module: nn.Module, images: torch.Tensor, channels, rf: bool = True,
+                                composite: str = "epsilon_plus_flat", epsilon: float = 1e-6, norm_pass: bool = False) -> torch.Tensor:
+    """Input relevance ``(B, Cin, H, W)`` of one channel per row, conditioned at ``module``'s output (crp's
+    ``CondAttribution`` with ``{layer: [channel]}``, what the reference's ``get_max_reference`` renders).
+
+    The start relevance at the hooked output ``a`` is ``sl_condition_init(a, channels, rf)``: ``rf`` keeps ``a`` at the
+    channel's first argmax position only (the receptive-field heatmap), else the whole channel.  It is sent back to the
+    input with ``autograd.grad``: under ``composite="epsilon_plus_flat"`` / ``"epsilon_plus_flat_normpass"`` the rules
+    above make the "gradient" that reaches the input its relevance; under ``"gradient_x_activation"`` the input gradient is
+    multiplied by the input.  A callable attribution returns layer relevance only and cannot be conditioned here.
+    Every row is independent of the others (no batch statistics in eval mode), so the result does not depend on how
+    (image, channel) pairs are batched."""
+    from semanticlens_amd import _native as N
+
+    if callable(composite):
+        raise NotImplementedError("a callable attribution returns layer relevance only; conditional input heatmaps need "
+                                  "composite='epsilon_plus_flat', 'epsilon_plus_flat_normpass' or 'gradient_x_activation'")
+    if composite in ("epsilon_plus_flat", "epsilon_plus_flat_normpass"):
+        rules = epsilon_plus_flat(model, epsilon, norm_pass=norm_pass or composite.endswith("_normpass"))
+    elif composite == "gradient_x_activation":
+        rules = nullcontext()
+    else:
+        raise ValueError(f"unknown composite {composite!r}")
+    kept: list[torch.Tensor] = []
+    with rules:
+        # registered AFTER the rule hooks, so the kept output is the tensor the rule's autograd node produced
+        handle = module.register_forward_hook(lambda m, i, o: kept.append(o))
+        try:
+            with torch.enable_grad():
+                x = images.detach().requires_grad_(True)
+                model(x)
+                if not kept or not torch.is_tensor(kept[0]) or not kept[0].requires_grad:
+                    raise RuntimeError("the conditioned layer produced no tensor connected to the input")
+                a = kept[0]
+                start = N.condition_init(a, channels, rf)
+                (g,) = torch.autograd.grad(a, x, grad_outputs=start)
+        finally:
+            handle.remove()
+    g = g.detach()
+    return g if composite != "gradient_x_activation" else g * x.detach()
