@@ -364,6 +364,15 @@ int sl_preprocess_plan(const int32_t* h_hw, const int64_t* h_pixel_offsets, int6
 int sl_preprocess(const uint8_t* d_pixels, const int64_t* d_plan, int64_t B, int S, int interp, int64_t max_h,
                   int64_t coef_bytes, const float* h_mean, const float* h_std, float* d_out, uint8_t* d_out_u8,
                   void* d_ws, size_t ws_bytes, void* stream);
+/* Plan entries for P sub-rectangles of N packed images (host): h_hw (N,2) int32 the full images' heights/widths,
+ * h_pixel_offsets (N) their byte offsets (NULL: tightly packed in order), h_index (P) int64 the image of each pair,
+ * h_box (P,4) int32 {row1, row2, col1, col2} (ends exclusive; clamped to the image, must stay non-empty).  Each entry reads
+ * only its box (plan slot 12: the source row stride in bytes) and sl_preprocess then yields, bit for bit, the transform
+ * of the cropped image (`pil.crop((col1, row1, col2, row2))`: crop, then resize).  h_info as for sl_preprocess_plan
+ * (SL_PP_INFO_PIXEL_BYTES: the packed buffer's extent). */
+int sl_preprocess_plan_rois(const int32_t* h_hw, const int64_t* h_pixel_offsets, int64_t N, const int64_t* h_index,
+                            const int32_t* h_box, int64_t P, int S, int resize_mode, int interp, int64_t* h_plan,
+                            int64_t* h_info);
 
 /* ---- K13: concept-conditional heatmaps and rendered reference crops ------------
  * sl_render_heatmaps replaces the per-image host loop of the reference's three plot functions
@@ -395,6 +404,22 @@ int sl_render_heatmaps(const float* d_rel, int64_t B, int64_t Cin, int64_t H, in
  * [0, C) leaves its row zero (callers validate). */
 int sl_condition_init(const float* d_act, int64_t B, int64_t C, int64_t S, int64_t sb, int64_t sc, int64_t ss,
                       const int64_t* d_channels, int rf, float* d_out, int64_t ob, int64_t oc, int64_t os, void* stream);
+
+/* ---- K14: crop boxes of heatmaps without a canvas -------------------------------------
+ * sl_activation_heat_boxes: P pairs (row d_rows[j], channel d_channels[j]) (int64, device) of a layer output d_act
+ * (B,C,S) strided fp32 (sl_condition_init's convention; conv: S = H'*W', prefix 0, grid H' x W'; tokens: the (B,F,T)
+ * view, the grid gh x gw starting at token `prefix`).  heat_j = max(bilinear upsample of act[u_j, c_j] to H x W
+ * (F.interpolate, align_corners=False), 0); d_box (P,4) int32 = the box sl_render_heatmaps computes for that heat in
+ * SL_RENDER_CROP style (blur, |b| / max|b|, crop range, square box; the full image when nothing exceeds crop_th).
+ * d_heat (P,H,W) the unblurred heat, written only when non-NULL.  sl_heat_boxes: the same box from a full-resolution
+ * d_heat (P,H,W).  d_ws: sl_render_ws_bytes(P, H, W) bytes.  Refused before any launch as sl_render_heatmaps refuses
+ * kernel_size and crop_th; out-of-range rows / channels read as an all-zero map (callers validate). */
+int sl_activation_heat_boxes(const float* d_act, int64_t B, int64_t C, int64_t S, int64_t sb, int64_t sc, int64_t ss,
+                             int64_t prefix, int64_t gh, int64_t gw, const int64_t* d_rows, const int64_t* d_channels,
+                             int64_t P, int64_t H, int64_t W, int kernel_size, float crop_th, float* d_heat, int32_t* d_box,
+                             void* d_ws, size_t ws_bytes, void* stream);
+int sl_heat_boxes(const float* d_heat, int64_t P, int64_t H, int64_t W, int kernel_size, float crop_th, int32_t* d_box,
+                  void* d_ws, size_t ws_bytes, void* stream);
 
 /* ---- measurement --------------------------------------------------------------------------
  * When enabled, every launch of a profiled kernel family is bracketed by HIP events on its

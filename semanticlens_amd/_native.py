@@ -106,6 +106,10 @@ SIGNATURES = {
     "sl_render_heatmaps": (_int, [_vp, _i64, _i64, _i64, _i64, _vp, _int, ctypes.c_float, ctypes.c_float, ctypes.c_double, _int, _int,
                                   _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "sl_condition_init": (_int, [_vp, _i64, _i64, _i64, _i64, _i64, _i64, _vp, _int, _vp, _i64, _i64, _i64, _vp]),
+    "sl_preprocess_plan_rois": (_int, [_vp, _vp, _i64, _vp, _vp, _i64, _int, _int, _int, _vp, _vp]),
+    "sl_activation_heat_boxes": (_int, [_vp, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _i64, _i64, _i64, _int,
+                                        ctypes.c_float, _vp, _vp, _vp, _sz, _vp]),
+    "sl_heat_boxes": (_int, [_vp, _i64, _i64, _i64, _int, ctypes.c_float, _vp, _vp, _sz, _vp]),
     "sl_prof_enable": (_int, [_int]),
     "sl_prof_reset": (_int, []),
     "sl_prof_read": (_int, [_int, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(_i64), ctypes.POINTER(ctypes.c_double)]),
@@ -1082,6 +1086,29 @@ def preprocess_plan(hw, size: int, resize_mode: str = "shortest", interp: str = 
     return plan, {"ws_bytes": int(info[0]), "coef_bytes": int(info[1]), "max_h": int(info[2]), "pixel_bytes": int(info[3])}
 
 
+def preprocess_plan_rois(hw, boxes, index, size: int, resize_mode: str = "shortest", interp: str = "bicubic",
+                         pixel_offsets=None):
+    """Plan entries for sub-rectangles: ``hw`` (N, 2) the packed images' heights/widths, ``boxes`` (P, 4) (row1, row2, col1,
+    col2) clamped to the image (must stay non-empty), ``index`` (P,) the image of each box -> (plan (P, 16) int64 CPU
+    tensor, info dict) for :func:`preprocess`; each result equals the transform of the cropped image."""
+    hw_t = torch.as_tensor(hw, dtype=torch.int32).reshape(-1, 2).contiguous()
+    box = torch.as_tensor(boxes, dtype=torch.int32).reshape(-1, 4).contiguous()
+    idx = torch.as_tensor(index, dtype=torch.int64).reshape(-1).contiguous()
+    if idx.shape[0] != box.shape[0]:
+        raise ValueError(f"preprocess_plan_rois: {box.shape[0]} boxes for {idx.shape[0]} indices")
+    if resize_mode not in PP_RESIZE_MODES or interp not in PP_INTERP:
+        raise ValueError(f"unknown resize_mode/interpolation {resize_mode!r}/{interp!r}")
+    N_, P = hw_t.shape[0], box.shape[0]
+    plan = torch.zeros((P, SL_PP_PLAN_STRIDE), dtype=torch.int64)
+    info = (ctypes.c_int64 * 4)()
+    off = None if pixel_offsets is None else torch.as_tensor(pixel_offsets, dtype=torch.int64).contiguous()
+    _check(lib().sl_preprocess_plan_rois(_vp(hw_t.data_ptr()) if N_ else _vp(None), _vp(off.data_ptr()) if off is not None and N_ else _vp(None),
+                                         N_, _vp(idx.data_ptr()) if P else _vp(None), _vp(box.data_ptr()) if P else _vp(None), P,
+                                         int(size), PP_RESIZE_MODES[resize_mode], PP_INTERP[interp],
+                                         _vp(plan.data_ptr()) if P else _vp(None), ctypes.cast(info, _vp)), "sl_preprocess_plan_rois")
+    return plan, {"ws_bytes": int(info[0]), "coef_bytes": int(info[1]), "max_h": int(info[2]), "pixel_bytes": int(info[3])}
+
+
 def preprocess(pixels: torch.Tensor, plan: torch.Tensor, info: dict, size: int, mean, std, interp: str = "bicubic",
                want_u8: bool = False, want_f32: bool = True):
     """Packed raw RGB bytes on the device + uploaded plan -> (B, 3, size, size) fp32 (and/or (B, size, size, 3) uint8)."""
@@ -1173,3 +1200,98 @@ def condition_init(act: torch.Tensor, channels, rf: bool) -> torch.Tensor:
         _check(lib().sl_condition_init(_ptr(x), B, C, S, sb, sc, ss, _ptr(ch_d), int(bool(rf)), _ptr(out), ob, oc, os_, _stream(x)),
                "sl_condition_init")
     return out if act.dtype == torch.float32 else out.to(act.dtype)
+
+
+# ------------------------------------------------------------------------------------------------
+# K14: crop boxes of heatmaps without a canvas
+# ------------------------------------------------------------------------------------------------
+def check_crop_args(crop_th: float, kernel_size: int, H: int | None = None, W: int | None = None):
+    """The limits K14 (and K13) put on the crop arguments, checked on the host before anything runs."""
+    if not (isinstance(kernel_size, int) and not isinstance(kernel_size, bool)) or kernel_size < 1 or kernel_size % 2 == 0:
+        raise ValueError(f"kernel_size must be an odd positive integer, got {kernel_size!r}")
+    if kernel_size > 255:
+        raise ValueError(f"kernel_size must be at most 255, got {kernel_size}")
+    if not (0.0 <= float(crop_th) < 1.0):
+        raise ValueError("'crop_th' must be between [0, 1)")
+    if H is not None and W is not None and not (kernel_size // 2 < H and kernel_size // 2 < W):
+        raise ValueError(f"kernel_size // 2 = {kernel_size // 2} must be smaller than H and W ({H} x {W}) for reflect padding")
+
+
+def _layer_view(x: torch.Tensor):
+    """A layer output as the (B, C, S) strided view of sl_condition_init: (x, B, C, S, sb, sc, ss, conv grid or None)."""
+    if x.ndim == 4:
+        B, C, H, W = x.shape
+        x, sb, sc, ss = _flatten_spatial(x)
+        return x, B, C, H * W, sb, sc, ss, (H, W)
+    if x.ndim == 3:  # tokens (B, T, F): the (B, F, T) view
+        B, T, C = x.shape
+        sb, ss, sc = x.stride()
+        return x, B, C, T, sb, sc, ss, None
+    if x.ndim == 2:
+        B, C = x.shape
+        sb, sc = x.stride()
+        return x, B, C, 1, sb, sc, 1, (1, 1)
+    raise ValueError(f"layer outputs must be 2-, 3- or 4-D, got {x.ndim}-D")
+
+
+def activation_heat_boxes(act: torch.Tensor, rows, channels, size, kernel_size: int = 51, crop_th: float = 0.01,
+                          token_grid=None, prefix_tokens: int = 0, want_heat: bool = False):
+    """K14 on a layer output ``act`` ((B, C, H', W'), (B, T, F) tokens with ``token_grid`` (gh, gw) starting at token
+    ``prefix_tokens``, or (B, C)) for the pairs (``rows[j]``, ``channels[j]``) at model input ``size`` (H, W) ->
+    ``(heat (P, H, W) fp32 or None, box (P, 4) int32)`` on the device.  heat = max(bilinear upsample, 0); box = the
+    CROP-style square box of ``render_heatmaps`` on that heat.  fp32 only (other dtypes are cast, as ``condition_init``)."""
+    if not act.is_cuda:
+        raise TypeError(f"activation_heat_boxes: expected a tensor on a HIP device, got {act.device}")
+    H, W = (int(v) for v in size)
+    check_crop_args(crop_th, kernel_size, H, W)
+    x = act.detach()
+    if x.dtype != torch.float32:
+        x = x.float()
+    x, B, C, S, sb, sc, ss, grid = _layer_view(x)
+    prefix = 0
+    if grid is None:
+        if token_grid is None:
+            raise ValueError("activation_heat_boxes: token layers need token_grid")
+        grid, prefix = (int(token_grid[0]), int(token_grid[1])), int(prefix_tokens or 0)
+        if grid[0] < 1 or grid[1] < 1 or prefix < 0 or prefix + grid[0] * grid[1] > S:
+            raise ValueError(f"activation_heat_boxes: prefix_tokens {prefix} + token_grid {grid} does not fit {S} tokens")
+    r = torch.as_tensor(rows, dtype=torch.int64).reshape(-1)
+    ch = torch.as_tensor(channels, dtype=torch.int64).reshape(-1)
+    if r.numel() != ch.numel():
+        raise ValueError(f"activation_heat_boxes: {r.numel()} rows for {ch.numel()} channels")
+    if r.numel() and not r.is_cuda and (int(r.min()) < 0 or int(r.max()) >= B):
+        raise ValueError(f"activation_heat_boxes: rows must lie in [0, {B})")
+    if ch.numel() and not ch.is_cuda and (int(ch.min()) < 0 or int(ch.max()) >= C):
+        raise ValueError(f"activation_heat_boxes: channel ids must lie in [0, {C})")
+    dev = x.device
+    P = r.numel()
+    heat = torch.empty((P, H, W), dtype=torch.float32, device=dev) if want_heat else None
+    box = torch.empty((P, 4), dtype=torch.int32, device=dev)
+    if P == 0:
+        return heat, box
+    ws_bytes = lib().sl_render_ws_bytes(P, H, W)
+    ws = torch.empty((max(ws_bytes, 16),), dtype=torch.uint8, device=dev)
+    r_d, ch_d = r.to(dev, non_blocking=True), ch.to(dev, non_blocking=True)
+    with _on(dev):
+        _check(lib().sl_activation_heat_boxes(_ptr(x), B, C, S, sb, sc, ss, prefix, grid[0], grid[1], _ptr(r_d), _ptr(ch_d), P, H, W,
+                                              int(kernel_size), float(crop_th), _ptr(heat), _ptr(box), _ptr(ws), ws_bytes, _stream(x)),
+               "sl_activation_heat_boxes")
+    return heat, box
+
+
+def heat_boxes(heat: torch.Tensor, kernel_size: int = 51, crop_th: float = 0.01) -> torch.Tensor:
+    """K14 on full-resolution heat (P, H, W) on the device -> box (P, 4) int32 (the CROP-style box of ``render_heatmaps``)."""
+    if not heat.is_cuda or heat.ndim != 3:
+        raise ValueError(f"heat_boxes: expected (P, H, W) on a HIP device, got {tuple(heat.shape)} on {heat.device}")
+    P, H, W = heat.shape
+    check_crop_args(crop_th, kernel_size, H, W)
+    h = heat.detach().to(torch.float32).contiguous()
+    box = torch.empty((P, 4), dtype=torch.int32, device=h.device)
+    if P == 0:
+        return box
+    ws_bytes = lib().sl_render_ws_bytes(P, H, W)
+    ws = torch.empty((max(ws_bytes, 16),), dtype=torch.uint8, device=h.device)
+    with _on(h.device):
+        _check(lib().sl_heat_boxes(_ptr(h), P, H, W, int(kernel_size), float(crop_th), _ptr(box), _ptr(ws), ws_bytes, _stream(h)),
+               "sl_heat_boxes")
+    return box

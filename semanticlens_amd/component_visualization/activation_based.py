@@ -260,7 +260,8 @@ class ActivationComponentVisualizer(AbstractComponentVisualizer):
     # ---- hot loop 2 + gather (activation_based.py:360-451) ---------------------------------------
     @torch.no_grad()
     def _compute_concept_db(self, fm, batch_size=32, keep_on_device: bool = False, referenced_only: bool = False,
-                            single_pass: bool = False, **kwargs):
+                            single_pass: bool = False, crop: bool = False, crop_th: float = 0.01, kernel_size: int = 51,
+                            token_grid=None, prefix_tokens=None, **kwargs):
         """``{layer: (n_components, n_samples, D)}`` = embeddings of each component's top samples.
 
         Returns host tensors like the reference unless ``keep_on_device`` is set.  ``referenced_only`` embeds only the
@@ -271,7 +272,20 @@ class ActivationComponentVisualizer(AbstractComponentVisualizer):
         time: forward + collect on the current HIP stream, the embedding of the same batch on a second stream beside it
         (the reference makes two sequential passes, activation_based.py:341-358 then :392-433); same top-k states and
         concept DB, +6 % throughput in ``bench.py``.  When the top-k cache exists only the embedding pass runs.
+
+        ``crop=True``: row ``[c, j]`` embeds reference sample ``j`` of component ``c`` cropped to the box of its heatmap for
+        ``c`` (the positive part of the upsampled channel map; ``crop_th`` / ``kernel_size`` as in ``crop_and_mask_images``,
+        ``token_grid`` / ``prefix_tokens`` for token layers, see :meth:`compute_heatmaps`); only referenced samples are
+        forwarded and embedded, ``single_pass`` and ``referenced_only`` are ignored, and ``run()`` is called only when the
+        top-k states are not collected yet (``crop_db.py``).
         """
+        if crop:
+            from semanticlens_amd.component_visualization.crop_db import activation_crop_db
+
+            N.check_crop_args(crop_th, kernel_size)
+            if not all(self.actmax_cache.cache[name].is_setup for name in self.layer_names):
+                self.run(batch_size=batch_size, **{k: v for k, v in kwargs.items() if k == "num_workers"})
+            return activation_crop_db(self, fm, batch_size, keep_on_device, crop_th, kernel_size, token_grid, prefix_tokens)
         if single_pass and not referenced_only:
             embeds = self._collect_and_embed_single_pass(fm, batch_size, **kwargs)
         else:
@@ -391,6 +405,42 @@ class ActivationComponentVisualizer(AbstractComponentVisualizer):
         """``(n_components, n_samples)`` int64 dataset indices (``-1`` = slot never filled)."""
         self._check_layer_name(layer_name)
         return self.actmax_cache.cache[layer_name].sample_ids
+
+    @torch.no_grad()
+    def compute_heatmaps(self, concept_ids, layer_name: str, n_ref: int, batch_size: int = 32, token_grid=None,
+                         prefix_tokens=None) -> dict:
+        """``{concept_id: (ids (n_ref,) int64, heat (n_ref, H, W) fp32 on the device)}``: the activation heatmap of each of
+        the first ``n_ref`` reference samples of each concept — channel ``concept_id`` of ``layer_name``'s output,
+        bilinearly upsampled to the model input ``(H, W)`` (``F.interpolate``, ``align_corners=False``), negative values
+        set to 0 (K14).  Token layers ``(B, T, F)`` read a ``token_grid`` = (gh, gw) patch grid after ``prefix_tokens``
+        leading tokens, inferred when ``T`` or ``T - 1`` is a perfect square.  (concept, sample) pairs of different
+        concepts share forwards of ``batch_size`` samples; the forward stops after ``layer_name``."""
+        from semanticlens_amd.component_visualization.crop_db import forward_heat_boxes
+
+        self._check_layer_name(layer_name)
+        concepts = [int(c) for c in torch.as_tensor(concept_ids).reshape(-1).tolist()]
+        all_ids = self.get_max_reference(layer_name)
+        n_ref = int(n_ref)
+        if n_ref < 1 or n_ref > all_ids.shape[1]:
+            raise ValueError(f"n_ref must lie in [1, {all_ids.shape[1]}] (num_samples), got {n_ref}")
+        bad = [c for c in concepts if c < 0 or c >= all_ids.shape[0]]
+        if bad:
+            raise ValueError(f"concept ids {bad} out of range for {layer_name!r} ({all_ids.shape[0]} components)")
+        ids = {c: all_ids[c, :n_ref].to(torch.int64).cpu() for c in concepts}
+        if any(bool((v < 0).any()) for v in ids.values()):
+            raise ValueError(f"fewer than n_ref={n_ref} reference samples were collected for some of {concepts}")
+        pairs = [(c, int(i)) for c in concepts for i in ids[c]]
+        heats = []
+        for s in range(0, len(pairs), batch_size):
+            chunk = pairs[s:s + batch_size]
+            rows = torch.arange(len(chunk), dtype=torch.int64)
+            chans = torch.tensor([c for c, _ in chunk], dtype=torch.int64)
+            # kernel_size 1: the box K14 computes beside the heat is not used here
+            res, _ = forward_heat_boxes(self, [i for _, i in chunk], {layer_name: (rows, chans)}, 1, 0.0, token_grid, prefix_tokens,
+                                        want_heat=True)
+            heats.append(res[layer_name][0])
+        heat = torch.cat(heats)
+        return {c: (ids[c], heat[k * n_ref:(k + 1) * n_ref]) for k, c in enumerate(concepts)}
 
     def visualize_components(self, component_ids, layer_name: str, n_samples: int = 9, nrows: int = 3, fname=None,
                              denormalization_fn=None):

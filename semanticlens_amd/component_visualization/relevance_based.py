@@ -314,8 +314,6 @@ class RelevanceComponentVisualizer(ActivationComponentVisualizer):
         samples of each concept, ``mode`` choosing the ranking (``"activation"``, the reference's choice, or
         ``"relevance"``), ``rf`` the receptive-field condition (see ``lrp.conditional_input_relevance``).  (concept,
         sample) pairs of different concepts share batches of ``batch_size``; the result does not depend on it."""
-        from semanticlens_amd.component_visualization.lrp import conditional_input_relevance
-
         self._check_layer_name(layer_name)
         if mode not in ("activation", "relevance"):
             raise ValueError(f"mode must be 'activation' or 'relevance', got {mode!r}")
@@ -334,6 +332,13 @@ class RelevanceComponentVisualizer(ActivationComponentVisualizer):
         if any(bool((v < 0).any()) for v in ids.values()):
             raise ValueError(f"fewer than n_ref={n_ref} reference samples were collected for some of {concepts}")
         pairs = [(c, int(i)) for c in concepts for i in ids[c]]
+        heat = self._conditional_heat(layer_name, pairs, rf=rf, batch_size=batch_size)
+        return {c: (ids[c], heat[k * n_ref:(k + 1) * n_ref]) for k, c in enumerate(concepts)}
+
+    def _conditional_heat(self, layer_name: str, pairs, rf: bool, batch_size: int) -> torch.Tensor:
+        """``(P, H, W)`` conditional input heatmaps of (concept, sample id) ``pairs`` in batches of ``batch_size`` pairs."""
+        from semanticlens_amd.component_visualization.lrp import conditional_input_relevance
+
         composite = self._cond_composite
         if callable(composite):
             raise NotImplementedError("compute_heatmaps needs composite='epsilon_plus_flat', 'epsilon_plus_flat_normpass' or "
@@ -346,8 +351,7 @@ class RelevanceComponentVisualizer(ActivationComponentVisualizer):
             rel = conditional_input_relevance(self.model, module, images, [c for c, _ in chunk], rf=rf, composite=composite,
                                               epsilon=self._cond_epsilon)
             heats.append(rel.sum(1))
-        heat = torch.cat(heats)
-        return {c: (ids[c], heat[k * n_ref:(k + 1) * n_ref]) for k, c in enumerate(concepts)}
+        return torch.cat(heats)
 
     def get_act_max_sample_ids(self, layer_name: str) -> torch.Tensor:
         """The reference's accessor (relevance_based.py:283-298): activation-mode sample ids, ``(n_components, n)``."""
@@ -361,10 +365,21 @@ class RelevanceComponentVisualizer(ActivationComponentVisualizer):
         return {**self.actmax_cache.metadata, "abs_norm": str(self.abs_norm), "composite": str(self.composite),
                 "dataset": self.dataset.name, "model": self.model.name}
 
-    def _compute_concept_db(self, fm, batch_size=32, keep_on_device: bool = False, **kwargs):
-        """``{layer: (n_components, num_samples, D)}`` of the relevance-mode reference samples."""
+    def _compute_concept_db(self, fm, batch_size=32, keep_on_device: bool = False, crop: bool = False, crop_th: float = 0.01,
+                            kernel_size: int = 51, token_grid=None, prefix_tokens=None, **kwargs):
+        """``{layer: (n_components, num_samples, D)}`` of the relevance-mode reference samples.  ``crop=True``: each
+        sample cropped to the box of its receptive-field conditional relevance heatmap (:meth:`compute_heatmaps` with
+        ``mode="relevance"``, ``rf=True``; ``crop_db.py``); ``token_grid`` / ``prefix_tokens`` are not
+        needed (the heatmap lives on the input)."""
         kwargs.pop("single_pass", None)  # the collect pass needs a backward: always two passes
         kwargs.pop("referenced_only", None)
+        if crop:
+            from semanticlens_amd.component_visualization.crop_db import relevance_crop_db
+
+            N.check_crop_args(crop_th, kernel_size)
+            if not self.check_if_preprocessed():
+                self.run(batch_size=batch_size, **{k: v for k, v in kwargs.items() if k == "num_workers"})
+            return relevance_crop_db(self, fm, batch_size, keep_on_device, crop_th, kernel_size)
         self.run(batch_size=batch_size, **{k: v for k, v in kwargs.items() if k == "num_workers"})
         embeds = self._embed_vision_dataset(fm, batch_size, **kwargs)
         out = {}

@@ -11,7 +11,11 @@
 //   vertical_kernel    second pass over the intermediate, then (u / 255 - mean) / std as three IEEE fp32 operations
 // Results are bit-identical to PIL + torchvision (tests/golden/preprocess.npz).  Integer/byte work, bound by the
 // read of the source pixels.
+// sl_preprocess_plan_rois writes the same plan entries for sub-rectangles of packed images (crop, then resize: equal to
+// the transform of `pil.crop(box)`); an entry's source row stride (P_ROW_BYTES) is then the whole image's row.
 #include "common.hpp"
+
+#include <vector>
 
 namespace sl {
 namespace {
@@ -19,6 +23,7 @@ namespace {
 constexpr int kPrecisionBits = 32 - 8 - 2;
 constexpr int kPlanStride = SL_PP_PLAN_STRIDE;
 enum { P_OFF = 0, P_H, P_W, P_OH, P_OW, P_TOP, P_LEFT, P_KH, P_KV, P_COEF_H, P_COEF_V, P_TMP };
+constexpr int P_ROW_BYTES = 12;  // source row stride in bytes; 0 = w * 3 (a whole image; ROI entries read a sub-rectangle)
 
 struct Norm {
   float mean[3], stdv[3];
@@ -169,8 +174,8 @@ __global__ __launch_bounds__(256) void horizontal_kernel(const uint8_t* __restri
   const int xmin = bounds[2 * j];
   const int xflag = bounds[2 * j + 1];
   const int xmax = xflag & ~kWideFlag;
-  const int64_t row_bytes = (int64_t)w * 3;
-  const uint8_t* src = pixels + p[P_OFF] + ((int64_t)y0 * w + xmin) * 3;
+  const int64_t row_bytes = p[P_ROW_BYTES] ? p[P_ROW_BYTES] : (int64_t)w * 3;
+  const uint8_t* src = pixels + p[P_OFF] + (int64_t)y0 * row_bytes + (int64_t)xmin * 3;
   int acc[R][3];
 #pragma unroll
   for (int r = 0; r < R; ++r) acc[r][0] = acc[r][1] = acc[r][2] = 1 << (kPrecisionBits - 1);
@@ -295,6 +300,43 @@ __global__ __launch_bounds__(256) void vertical_kernel(const int64_t* __restrict
 
 inline size_t align16(size_t v) { return (v + 15) & ~(size_t)15; }
 
+// one plan entry for an h x w source at byte offset `off` with row stride `row_bytes` (0: w * 3); advances the coefficient
+// and intermediate offsets and the tallest source
+int plan_entry(int64_t h, int64_t w, int64_t off, int64_t row_bytes, int S, int resize_mode, int interp, int64_t* p, int64_t& coef,
+               size_t& tmp, int64_t& mh) {
+  int64_t oh = S, ow = S;
+  if (resize_mode == SL_PP_SHORTEST) {  // torchvision Resize(int): shorter edge -> S, other edge int(S * long / short)
+    const int64_t shrt = w <= h ? w : h, lng = w <= h ? h : w;
+    const int64_t new_long = (int64_t)((double)(S * lng) / (double)shrt);
+    if (w <= h) oh = new_long;
+    else ow = new_long;
+  }
+  auto crop = [](int64_t size, int64_t c) {  // int(round((size - c) / 2.0)), round half to even
+    const int64_t d = size - c, fl = d >= 0 ? d / 2 : -((-d + 1) / 2);
+    if ((d & 1) == 0) return fl;
+    return (fl & 1) ? fl + 1 : fl;
+  };
+  for (int i = 0; i < kPlanStride; ++i) p[i] = 0;
+  p[P_OFF] = off;
+  p[P_H] = h;
+  p[P_W] = w;
+  p[P_OH] = oh;
+  p[P_OW] = ow;
+  p[P_ROW_BYTES] = row_bytes;
+  p[P_TOP] = crop(oh, S);
+  p[P_LEFT] = crop(ow, S);
+  p[P_KH] = axis_ksize((int)w, (int)ow, interp);
+  p[P_KV] = axis_ksize((int)h, (int)oh, interp);
+  p[P_COEF_H] = coef;
+  coef += pad4(2 * S) + (int64_t)S * pad4((int)p[P_KH]);
+  p[P_COEF_V] = coef;
+  coef += pad4(2 * S) + (int64_t)S * pad4((int)p[P_KV]);
+  p[P_TMP] = (int64_t)tmp;
+  tmp += align16((size_t)h * (size_t)S * 3);
+  if (h > mh) mh = h;
+  return 0;
+}
+
 }  // namespace
 }  // namespace sl
 
@@ -312,40 +354,56 @@ SL_API int sl_preprocess_plan(const int32_t* h_hw, const int64_t* h_pixel_offset
     const int64_t h = h_hw[2 * b], w = h_hw[2 * b + 1];
     SL_REQUIRE(h >= 1 && w >= 1 && h < (1 << 24) && w < (1 << 24), "sl_preprocess_plan: image %lld has size %lld x %lld",
                (long long)b, (long long)h, (long long)w);
-    int64_t oh = S, ow = S;
-    if (resize_mode == SL_PP_SHORTEST) {  // torchvision Resize(int): shorter edge -> S, other edge int(S * long / short)
-      const int64_t shrt = w <= h ? w : h, lng = w <= h ? h : w;
-      const int64_t new_long = (int64_t)((double)(S * lng) / (double)shrt);
-      if (w <= h) oh = new_long;
-      else ow = new_long;
-    }
-    auto crop = [](int64_t size, int64_t c) {  // int(round((size - c) / 2.0)), round half to even
-      const int64_t d = size - c, fl = d >= 0 ? d / 2 : -((-d + 1) / 2);
-      if ((d & 1) == 0) return fl;
-      return (fl & 1) ? fl + 1 : fl;
-    };
-    int64_t* p = h_plan + b * kPlanStride;
-    for (int i = 0; i < kPlanStride; ++i) p[i] = 0;
-    p[P_OFF] = h_pixel_offsets ? h_pixel_offsets[b] : pix;
-    p[P_H] = h;
-    p[P_W] = w;
-    p[P_OH] = oh;
-    p[P_OW] = ow;
-    SL_REQUIRE(oh >= S && ow >= S, "sl_preprocess_plan: resized image %lld smaller than the crop", (long long)b);
-    p[P_TOP] = crop(oh, S);
-    p[P_LEFT] = crop(ow, S);
-    p[P_KH] = axis_ksize((int)w, (int)ow, interp);
-    p[P_KV] = axis_ksize((int)h, (int)oh, interp);
-    p[P_COEF_H] = coef;
-    coef += pad4(2 * S) + (int64_t)S * pad4((int)p[P_KH]);
-    p[P_COEF_V] = coef;
-    coef += pad4(2 * S) + (int64_t)S * pad4((int)p[P_KV]);
-    p[P_TMP] = (int64_t)tmp;
-    tmp += align16((size_t)h * (size_t)S * 3);
+    const int rc = plan_entry(h, w, h_pixel_offsets ? h_pixel_offsets[b] : pix, 0, S, resize_mode, interp, h_plan + b * kPlanStride,
+                              coef, tmp, mh);
+    if (rc) return rc;
+    SL_REQUIRE(h_plan[b * kPlanStride + P_OH] >= S && h_plan[b * kPlanStride + P_OW] >= S,
+               "sl_preprocess_plan: resized image %lld smaller than the crop", (long long)b);
     pix += h * w * 3;
-    if (h > mh) mh = h;
   }
   // workspace: [coefficients int32][intermediate bytes]; P_TMP offsets are relative to the second region
+  h_info[SL_PP_INFO_COEF_BYTES] = (int64_t)align16((size_t)coef * 4);
+  h_info[SL_PP_INFO_WS_BYTES] = h_info[SL_PP_INFO_COEF_BYTES] + (int64_t)tmp;
+  h_info[SL_PP_INFO_MAX_H] = mh;
+  h_info[SL_PP_INFO_PIXEL_BYTES] = pix;
+  return 0;
+}
+
+SL_API int sl_preprocess_plan_rois(const int32_t* h_hw, const int64_t* h_pixel_offsets, int64_t N, const int64_t* h_index,
+                                   const int32_t* h_box, int64_t P, int S, int resize_mode, int interp, int64_t* h_plan,
+                                   int64_t* h_info) {
+  SL_REQUIRE(N >= 0 && P >= 0 && S >= 1, "sl_preprocess_plan_rois: bad shape");
+  SL_REQUIRE(resize_mode == SL_PP_SHORTEST || resize_mode == SL_PP_SQUASH, "sl_preprocess_plan_rois: unknown resize mode");
+  SL_REQUIRE(interp == SL_PP_BICUBIC || interp == SL_PP_BILINEAR, "sl_preprocess_plan_rois: unknown interpolation");
+  SL_REQUIRE(h_info && (N == 0 || h_hw) && (P == 0 || (h_index && h_box && h_plan)), "sl_preprocess_plan_rois: null pointer");
+  std::vector<int64_t> offs((size_t)N);  // byte offset of every source image
+  int64_t pix = 0;
+  for (int64_t n = 0; n < N; ++n) {
+    const int64_t h = h_hw[2 * n], w = h_hw[2 * n + 1];
+    SL_REQUIRE(h >= 1 && w >= 1 && h < (1 << 24) && w < (1 << 24), "sl_preprocess_plan_rois: image %lld has size %lld x %lld",
+               (long long)n, (long long)h, (long long)w);
+    SL_REQUIRE(!h_pixel_offsets || h_pixel_offsets[n] >= 0, "sl_preprocess_plan_rois: negative pixel offset");
+    offs[n] = h_pixel_offsets ? h_pixel_offsets[n] : pix;
+    const int64_t end = offs[n] + h * w * 3;
+    pix = end > pix ? end : pix;
+  }
+  int64_t coef = 0, mh = 0;
+  size_t tmp = 0;
+  for (int64_t j = 0; j < P; ++j) {
+    const int64_t n = h_index[j];
+    SL_REQUIRE(n >= 0 && n < N, "sl_preprocess_plan_rois: pair %lld refers to image %lld of %lld", (long long)j, (long long)n,
+               (long long)N);
+    const int64_t h = h_hw[2 * n], w = h_hw[2 * n + 1];
+    auto clamp = [](int64_t v, int64_t hi) { return v < 0 ? 0 : (v > hi ? hi : v); };
+    const int64_t r1 = clamp(h_box[4 * j], h), r2 = clamp(h_box[4 * j + 1], h), c1 = clamp(h_box[4 * j + 2], w),
+                  c2 = clamp(h_box[4 * j + 3], w);
+    SL_REQUIRE(r2 > r1 && c2 > c1, "sl_preprocess_plan_rois: box %lld (%d, %d, %d, %d) is empty inside its %lld x %lld image",
+               (long long)j, h_box[4 * j], h_box[4 * j + 1], h_box[4 * j + 2], h_box[4 * j + 3], (long long)h, (long long)w);
+    int64_t* p = h_plan + j * kPlanStride;
+    const int rc = plan_entry(r2 - r1, c2 - c1, offs[n] + (r1 * w + c1) * 3, w * 3, S, resize_mode, interp, p, coef, tmp, mh);
+    if (rc) return rc;
+    SL_REQUIRE(p[P_OH] >= S && p[P_OW] >= S, "sl_preprocess_plan_rois: resized crop %lld smaller than the crop", (long long)j);
+  }
   h_info[SL_PP_INFO_COEF_BYTES] = (int64_t)align16((size_t)coef * 4);
   h_info[SL_PP_INFO_WS_BYTES] = h_info[SL_PP_INFO_COEF_BYTES] + (int64_t)tmp;
   h_info[SL_PP_INFO_MAX_H] = mh;

@@ -586,6 +586,11 @@ class NativeClip(AbstractVLM):
     def device(self):
         return self._device
 
+    @property
+    def device_preprocess(self):
+        """The ``DevicePreprocess`` behind :meth:`preprocess`, or None when ``base``'s host transform runs."""
+        return self._preprocess
+
     def to(self, device):
         if torch.device(device).type != "cuda":
             raise N.NativeLibraryError("NativeClip runs on a HIP device only")
@@ -855,6 +860,11 @@ class NativeSigLip(AbstractVLM):
     def device(self):
         return self._device
 
+    @property
+    def device_preprocess(self):
+        """The ``DevicePreprocess`` behind :meth:`preprocess`, or None when ``base``'s host transform runs."""
+        return self._preprocess
+
     def to(self, device):
         if torch.device(device).type != "cuda":
             raise N.NativeLibraryError("NativeSigLip runs on a HIP device only")
@@ -913,6 +923,11 @@ class NativeTextClip(AbstractVLM):
     @property
     def device(self):
         return self._device
+
+    @property
+    def device_preprocess(self):
+        """The ``DevicePreprocess`` behind :meth:`preprocess`, or None when ``base``'s host transform runs."""
+        return self._preprocess
 
     def to(self, device):
         if torch.device(device).type != "cuda":

@@ -97,7 +97,9 @@ class DevicePreprocess:
         arrays = [_rgb_bytes(i) for i in imgs]
         hw = [a.shape[:2] for a in arrays]
         plan, info = N.preprocess_plan(hw, self.size, self.resize_mode, self.interpolation)
-        total = info["pixel_bytes"]
+        return self._stage(arrays, info["pixel_bytes"]), plan, info
+
+    def _stage(self, arrays, total):
         slot = self._slot = (getattr(self, "_slot", 1) + 1) % 2
         stage = self.__dict__.setdefault("_staging", [None, None])
         events = self.__dict__.setdefault("_events", [None, None])
@@ -110,7 +112,29 @@ class DevicePreprocess:
         buf = stage[slot][: max(total, 1)]
         if arrays:
             np.concatenate([a.reshape(-1) for a in arrays], out=buf.numpy()[:total])
-        return buf, plan, info
+        return buf
+
+    def _upload(self, buf, dev):
+        pixels = buf.to(dev, non_blocking=True)
+        if buf.is_pinned():  # the staging buffer may be rewritten once this upload is done
+            ev = torch.cuda.Event()
+            ev.record(torch.cuda.current_stream(dev))
+            self._events[self._slot] = ev
+        return pixels
+
+    def crops(self, images, boxes, index) -> torch.Tensor:
+        """``(P, 3, S, S)``: pair ``j`` is the transform of ``images[index[j]]`` cropped to ``boxes[j]`` = (row1, row2, col1,
+        col2) (ends exclusive, clamped to the image, non-empty after clamping) — bit for bit ``self([pil.crop((col1, row1,
+        col2, row2))])``: crop, then resize.  Every image is packed and uploaded once however many pairs refer to it."""
+        arrays = [_rgb_bytes(i) for i in images]
+        plan, info = N.preprocess_plan_rois([a.shape[:2] for a in arrays], boxes, index, self.size, self.resize_mode,
+                                            self.interpolation)
+        dev = self._device or N.default_device()
+        if plan.shape[0] == 0:
+            return torch.empty((0, 3, self.size, self.size), dtype=torch.float32, device=dev)
+        pixels = self._upload(self._stage(arrays, info["pixel_bytes"]), dev)
+        out, _ = N.preprocess(pixels, plan, info, self.size, self.mean, self.std, self.interpolation)
+        return out
 
     def __call__(self, img):
         single = not isinstance(img, (list, tuple))
@@ -119,11 +143,7 @@ class DevicePreprocess:
         imgs = [img] if single else list(img)
         dev = self._device or N.default_device()
         buf, plan, info = self.pack(imgs)
-        pixels = buf.to(dev, non_blocking=True)
-        if buf.is_pinned():  # the staging buffer may be rewritten once this upload is done
-            ev = torch.cuda.Event()
-            ev.record(torch.cuda.current_stream(dev))
-            self._events[self._slot] = ev
+        pixels = self._upload(buf, dev)
         out, _ = N.preprocess(pixels, plan, info, self.size, self.mean, self.std, self.interpolation)
         return out[0] if single else out
 

@@ -24,9 +24,9 @@ from semanticlens_amd.utils.helper import get_fallback_name
 logger = logging.getLogger(__name__)
 
 
-def compute_concept_db(cv: AbstractComponentVisualizer, fm: AbstractVLM):
-    """Stateless concept-DB build: delegates to ``cv._compute_concept_db(fm)`` (lens.py:27-56)."""
-    return cv._compute_concept_db(fm)
+def compute_concept_db(cv: AbstractComponentVisualizer, fm: AbstractVLM, **kwargs):
+    """Stateless concept-DB build: delegates to ``cv._compute_concept_db(fm, **kwargs)`` (lens.py:27-56)."""
+    return cv._compute_concept_db(fm, **kwargs)
 
 
 def text_probing(fm, query, aggregated_concept_db, templates=None, batch_size=None):
@@ -152,11 +152,16 @@ class Lens:
         """Build the concept DB through ``cv``, or load it from ``cv``'s cache directory.
 
         Cache file: ``<storage_dir>/concept_database/<fm.name>/concept_db-<metadata values except
-        dataset,model joined by '-'>.safetensors`` (lens.py:308-316).
+        dataset,model joined by '-'>.safetensors`` (lens.py:308-316).  ``crop=True`` (with ``crop_th``,
+        ``kernel_size``, ``token_grid``, ``prefix_tokens``) builds the DB from heatmap-cropped reference samples
+        (DESIGN.md §K14); its file stem ends in ``-crop-th<crop_th>-k<kernel_size>``.
         """
         if not cv.caching:
             return cv._compute_concept_db(self.fm, **kwargs)
-        path = self._concept_db_path(cv)
+        crop = bool(kwargs.get("crop", False))
+        if crop:
+            N.check_crop_args(kwargs.get("crop_th", 0.01), kwargs.get("kernel_size", 51))
+        path = self._concept_db_path(cv, crop=crop, crop_th=kwargs.get("crop_th", 0.01), kernel_size=kwargs.get("kernel_size", 51))
         if path.exists():
             logger.debug(f"concept DB read from {path}")
             return load_file(filename=path)
@@ -165,12 +170,15 @@ class Lens:
         logger.debug(f"concept DB written to {path}")
         return concept_db
 
-    def _concept_db_path(self, cv):
+    def _concept_db_path(self, cv, crop: bool = False, crop_th: float = 0.01, kernel_size: int = 51):
         """The cache file of ``cv``'s concept DB under this foundation model; creates its directory."""
         folder = cv.storage_dir / "concept_database" / self.fm.name
         folder.mkdir(parents=True, exist_ok=True)
         tags = [value for key, value in cv.metadata.items() if key not in ("dataset", "model")]
-        return folder / ("concept_db-" + "-".join(tags) + ".safetensors")
+        stem = "concept_db-" + "-".join(tags)
+        if crop:
+            stem += f"-crop-th{crop_th:g}-k{kernel_size}"
+        return folder / (stem + ".safetensors")
 
     def text_probing(self, query, aggregated_concept_db, templates=None, batch_size=None):
         return text_probing(self.fm, query, aggregated_concept_db, templates, batch_size)
