@@ -67,7 +67,8 @@ int sl_abi_version(void);
 /* number of HIP devices visible, or SL_E_HIP */
 /* Variant switches — which of several BIT-IDENTICAL kernel variants a dispatcher picks (0 = its own rule).  The parity tests walk the
  * variants with these; production code never needs them.  Names: "g3_tile" (split-bf16 GEMM tile: 128, 256, 8, 160, 64, 1280),
- * "f32_tile" (fp32-MFMA GEMM: 128, 8), "g3_strip_off" (1: no column-strip split), "colreduce_nw" (K2 waves per task: 4, 8, 16).
+ * "f32_tile" (fp32-MFMA GEMM: 128, 8), "g3_strip_off" (1: no column-strip split), "colreduce_nw" (K2 waves per task: 4, 8, 16),
+ * "bn_policy" (K16 cache policy: 1 plain, 2 non-temporal stores, 3 non-temporal loads and stores).
  * The environment variable SL_OPTIONS="name=value,..." presets them for a process; an explicit call wins.  No reference counterpart. */
 int sl_set_option(const char* name, int64_t value);
 int64_t sl_get_option(const char* name); /* -1 for an unknown name */
@@ -421,6 +422,17 @@ int sl_activation_heat_boxes(const float* d_act, int64_t B, int64_t C, int64_t S
 int sl_heat_boxes(const float* d_heat, int64_t P, int64_t H, int64_t W, int kernel_size, float crop_th, int32_t* d_box,
                   void* d_ws, size_t ws_bytes, void* stream);
 
+/* ---- K16: inference BatchNorm2d with its ReLU / residual add fused in -----------------
+ * d_x, d_y (and d_residual): contiguous NCHW fp32 (B,C,HW), 16-byte aligned, distinct buffers; d_mean, d_var, d_scale,
+ * d_bias: (C) fp32, read on every launch (nothing is folded or cached).  y = scale * ((x - mean) * rsqrt(var + eps)) + bias,
+ * bit for bit what MIOpen's inference BatchNorm writes; relu != 0 applies clamp_min(y, 0) (NaN and the sign of zero as ATen's);
+ * the _add_relu form computes clamp_min(y + residual, 0) with y rounded to fp32 first.  C <= 4096, B*C*HW < 2^31. */
+int sl_batchnorm_infer(const float* d_x, int64_t B, int64_t C, int64_t HW, const float* d_mean, const float* d_var,
+                       const float* d_scale, const float* d_bias, double eps, int relu, float* d_y, void* stream);
+int sl_batchnorm_infer_add_relu(const float* d_x, const float* d_residual, int64_t B, int64_t C, int64_t HW,
+                                const float* d_mean, const float* d_var, const float* d_scale, const float* d_bias,
+                                double eps, float* d_y, void* stream);
+
 /* ---- measurement --------------------------------------------------------------------------
  * When enabled, every launch of a profiled kernel family is bracketed by HIP events on its
  * own stream.  sl_prof_read synchronises those events and returns the totals. */
@@ -429,7 +441,8 @@ int sl_heat_boxes(const float* d_heat, int64_t P, int64_t H, int64_t W, int kern
 #define SL_PROF_GEMM 2   /* K6 cosine GEMM */
 #define SL_PROF_GATHER 3
 #define SL_PROF_SCORES 4
-#define SL_PROF_NFAM 5
+#define SL_PROF_BATCHNORM 5 /* K16 fused inference BatchNorm */
+#define SL_PROF_NFAM 6
 int sl_prof_enable(int on);
 int sl_prof_reset(void);
 /* total_ms: sum of event-bracketed durations; launches: count; bytes: algorithmic bytes

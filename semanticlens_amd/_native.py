@@ -22,7 +22,7 @@ SL_CONV_MAX, SL_CONV_MEAN, SL_CONV_SUM = 0, 1, 2
 SL_TOK_MEAN, SL_TOK_ABSMEAN, SL_TOK_MAX, SL_TOK_ABSMAX, SL_TOK_TOKEN = 0, 1, 2, 3, 4
 SL_TIES_TOTAL, SL_TIES_ATEN = 0, 1
 SL_MAX_SLOTS = 16
-SL_PROF_REDUCE, SL_PROF_MERGE, SL_PROF_GEMM, SL_PROF_GATHER, SL_PROF_SCORES = 0, 1, 2, 3, 4
+SL_PROF_REDUCE, SL_PROF_MERGE, SL_PROF_GEMM, SL_PROF_GATHER, SL_PROF_SCORES, SL_PROF_BATCHNORM = 0, 1, 2, 3, 4, 5
 SL_ACT_NONE, SL_ACT_GELU, SL_ACT_QUICKGELU, SL_ACT_GELU_TANH = 0, 1, 2, 3
 TIE_MODES = {"total": SL_TIES_TOTAL, "aten": SL_TIES_ATEN}
 SL_PP_PLAN_STRIDE = 16
@@ -110,6 +110,8 @@ SIGNATURES = {
     "sl_activation_heat_boxes": (_int, [_vp, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _i64, _i64, _i64, _int,
                                         ctypes.c_float, _vp, _vp, _vp, _sz, _vp]),
     "sl_heat_boxes": (_int, [_vp, _i64, _i64, _i64, _int, ctypes.c_float, _vp, _vp, _sz, _vp]),
+    "sl_batchnorm_infer": (_int, [_vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, ctypes.c_double, _int, _vp, _vp]),
+    "sl_batchnorm_infer_add_relu": (_int, [_vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, ctypes.c_double, _vp, _vp]),
     "sl_prof_enable": (_int, [_int]),
     "sl_prof_reset": (_int, []),
     "sl_prof_read": (_int, [_int, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(_i64), ctypes.POINTER(ctypes.c_double)]),
@@ -337,7 +339,7 @@ def actmax_merge(vals, ids, cand: torch.Tensor, slot_stride: int, id_bases: list
 
 
 def set_option(name: str, value: int) -> None:
-    """Force one of several bit-identical kernel variants (``g3_tile``, ``f32_tile``, ``g3_strip_off``, ``colreduce_nw``; 0 = the
+    """Force one of several bit-identical kernel variants (``g3_tile``, ``f32_tile``, ``g3_strip_off``, ``colreduce_nw``, ``bn_policy``; 0 = the
     dispatcher's own rule).  For the parity tests; ``SL_OPTIONS="name=value,..."`` presets them for a process."""
     _check(lib().sl_set_option(name.encode(), int(value)), "sl_set_option")
 
@@ -795,6 +797,32 @@ def template_mean(E: torch.Tensor, E0: torch.Tensor, Q: int) -> torch.Tensor:
     out = torch.empty((Q, D), dtype=torch.float32, device=Ed.device)
     with _on(Ed.device):
         _check(lib().sl_template_mean(_ptr(Ed), _ptr(E0d), Q, T, D, _ptr(out), _stream(Ed)), "sl_template_mean")
+    return out
+
+
+# ------------------------------------------------------------------------------------------------
+# K16
+# ------------------------------------------------------------------------------------------------
+BN_MAX_CHANNELS = 4096
+BN_MAX_ELEMENTS = (1 << 31) - 1
+
+
+def batchnorm_infer(x: torch.Tensor, mean: torch.Tensor, var: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, eps: float,
+                    relu: bool = False, residual: torch.Tensor | None = None) -> torch.Tensor:
+    """Inference BatchNorm2d of a contiguous NCHW fp32 device tensor into a fresh tensor, bit for bit what
+    ``F.batch_norm(..., training=False)`` gives, with ``relu_`` (``relu=True``) or ``relu_(y + residual)`` (``residual`` given) fused
+    in.  The caller has checked dtype, layout and alignment (``component_visualization/_bn_fuse.py``); the library re-checks what
+    it can see."""
+    B, C, H, W = x.shape
+    out = torch.empty_like(x)
+    with _on(x.device):
+        if residual is None:
+            rc = lib().sl_batchnorm_infer(_ptr(x), B, C, H * W, _ptr(mean), _ptr(var), _ptr(weight), _ptr(bias), float(eps),
+                                          1 if relu else 0, _ptr(out), _stream(x))
+        else:
+            rc = lib().sl_batchnorm_infer_add_relu(_ptr(x), _ptr(residual), B, C, H * W, _ptr(mean), _ptr(var), _ptr(weight),
+                                                   _ptr(bias), float(eps), _ptr(out), _stream(x))
+    _check(rc, "sl_batchnorm_infer")
     return out
 
 

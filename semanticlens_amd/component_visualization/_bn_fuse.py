@@ -1,0 +1,266 @@
+"""Run the probed model's inference BatchNorm2d on the library's K16 kernels while its hooks are registered.
+
+``substitute(model)`` swaps instance ``forward`` attributes and returns the function that removes them again; nothing else of
+the model is touched and outside the ``with`` block of :meth:`ActCache.hook_context` the model is exactly the user's.
+
+* Every plain ``BatchNorm2d`` gets a ``forward`` that calls ``sl_batchnorm_infer`` when the call is eligible and the class's
+  own ``forward`` otherwise.  The module is still *called*, so its hooks fire as before.
+* Every module that directly owns a ``BatchNorm2d`` is traced with ``torch.fx`` — all of its children are leaves, so they are
+  still called as modules and their hooks fire — and the patterns ``bn -> relu`` and ``bn -> add(., other) -> relu`` are replaced
+  by one fused call each.  A module that does not trace keeps its own ``forward``.
+
+Eligibility is decided per call (``_eligible``): eval mode with running statistics and affine parameters, fp32 on a HIP device,
+NCHW-contiguous, grad mode off, MIOpen enabled, and for the fused patterns no hook on the norm or the activation, whose separate
+outputs disappear.  Anything else runs the modules as the user wrote them.
+
+Proof before trust: the first time a site runs an epilogue, the same input also goes through ``F.batch_norm`` (+ add, ``relu_``)
+— the functional forms, so that no hook fires twice — and the bit patterns must be equal; otherwise the site is dropped with
+one warning.  Verified sites are kept per model (weakly), so a second visualizer over the same model pays nothing.
+
+``SEMANTICLENS_AMD_FUSE_BN=0`` switches all of this off.
+"""
+from __future__ import annotations
+
+import inspect
+import operator
+import os
+import warnings
+import weakref
+
+import torch
+import torch.nn as nn
+import torch.nn.functional as F
+
+from .. import _native as N
+
+_BN_FORWARD = nn.modules.batchnorm._BatchNorm.forward
+_PLANS: "weakref.WeakKeyDictionary[nn.Module, _Plan]" = weakref.WeakKeyDictionary()
+_ADDS = (operator.add, operator.iadd, torch.add)
+_RELUS = (F.relu, torch.relu, torch.relu_)
+
+
+def enabled() -> bool:
+    return os.environ.get("SEMANTICLENS_AMD_FUSE_BN", "1") != "0"
+
+
+def _plain_bn(m) -> bool:
+    return isinstance(m, nn.BatchNorm2d) and type(m).forward is _BN_FORWARD
+
+
+def _plain_relu(m) -> bool:
+    return isinstance(m, nn.ReLU) and type(m).forward is nn.ReLU.forward
+
+
+def _hooked(m: nn.Module) -> bool:
+    mod = nn.modules.module
+    return bool(m._forward_hooks or m._forward_pre_hooks or mod._global_forward_hooks or mod._global_forward_pre_hooks)
+
+
+def _streamable(t) -> bool:
+    """A contiguous NCHW fp32 device tensor the kernels read or write with 16-byte accesses."""
+    return (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype is torch.float32 and t.dim() == 4 and not t.requires_grad
+            and t.is_contiguous() and not t.is_contiguous(memory_format=torch.channels_last) and t.data_ptr() % 16 == 0)
+
+
+class _Site:
+    """One BatchNorm2d of the model: which epilogues were proven bit-equal on it, or that it was dropped."""
+
+    __slots__ = ("bn", "verified", "dropped")
+
+    def __init__(self, bn: nn.BatchNorm2d):
+        self.bn = bn
+        self.verified: set = set()
+        self.dropped = False
+
+    def eligible(self, x) -> bool:
+        bn = self.bn
+        if self.dropped or bn.training or torch.is_grad_enabled() or not enabled():
+            return False
+        if not _streamable(x) or not 0 < x.numel() <= N.BN_MAX_ELEMENTS or x.shape[1] > N.BN_MAX_CHANNELS:
+            return False
+        if not torch.backends.cudnn.enabled or torch.is_autocast_enabled():  # another BatchNorm kernel would have run
+            return False
+        for p in (bn.running_mean, bn.running_var, bn.weight, bn.bias):
+            if p is None or p.dtype is not torch.float32 or p.device != x.device or not p.is_contiguous() or p.numel() != x.shape[1]:
+                return False
+        return True
+
+    def run(self, x, relu: bool, other=None, bn_first: bool = True):
+        bn = self.bn
+        out = N.batchnorm_infer(x, bn.running_mean, bn.running_var, bn.weight, bn.bias, bn.eps, relu=relu, residual=other)
+        key = (relu, other is not None, (x.shape[2] * x.shape[3]) % 4 == 0)
+        if key in self.verified:
+            return out
+        ref = F.batch_norm(x, bn.running_mean, bn.running_var, bn.weight, bn.bias, False, 0.0, bn.eps)
+        if other is not None:
+            ref = ref + other if bn_first else other + ref
+        if relu:
+            ref = torch.relu_(ref)
+        if torch.equal(out.view(torch.int32), ref.view(torch.int32)):
+            self.verified.add(key)
+            return out
+        self.dropped = True
+        warnings.warn(
+            f"the fused BatchNorm kernel did not reproduce PyTorch's result bit for bit on a {tuple(x.shape)} input "
+            f"(relu={relu}, residual={other is not None}); this BatchNorm2d runs unfused from now on.", RuntimeWarning, stacklevel=3)
+        return ref
+
+
+def _bn_forward(site: _Site):
+    def forward(x):
+        if site.eligible(x):
+            return site.run(x, relu=False)
+        return _BN_FORWARD(site.bn, x)
+
+    return forward
+
+
+class _Fused(nn.Module):
+    """``relu(bn(x))`` or ``relu(add(bn(x), other))`` as one call; the modules themselves when the call is not eligible."""
+
+    def __init__(self, site: _Site, relu, add=None, bn_first: bool = True):
+        super().__init__()
+        self.__dict__.update(site=site, relu=relu, add=add, bn_first=bn_first)  # (not registered as children)
+
+    def forward(self, x, other=None):
+        site, relu = self.site, self.relu
+        ok = not _hooked(site.bn) and not (isinstance(relu, nn.Module) and _hooked(relu)) and site.eligible(x)
+        if ok and self.add is not None:
+            ok = _streamable(other) and other.shape == x.shape and other.device == x.device
+        if ok:
+            return site.run(x, relu=True, other=other, bn_first=self.bn_first)
+        out = site.bn(x)
+        if self.add is not None:
+            out = self.add(out, other) if self.bn_first else self.add(other, out)
+        return relu(out)
+
+
+def _trace(parent: nn.Module, sites: dict):
+    """GraphModule of ``parent``'s own forward with the fused patterns rewritten, or None."""
+    from torch import fx
+
+    class InplaceProxy(fx.Proxy):  # fx turns `a += b` into `a + b`; the graph must keep writing into `a`, which a caller may hold
+        pass
+
+    for name in ("iadd", "isub", "imul", "itruediv"):
+        op = getattr(operator, name)
+        setattr(InplaceProxy, f"__{name}__",
+                lambda self, other, op=op: self.tracer.create_proxy("call_function", op, (self, other), {}))
+
+    class LeafTracer(fx.Tracer):
+        def is_leaf_module(self, m, qualname):
+            return True
+
+        def proxy(self, node):
+            return InplaceProxy(node, self)
+
+    params = list(inspect.signature(parent.forward).parameters.values())
+    if any(p.kind is not p.POSITIONAL_OR_KEYWORD or p.default is not p.empty for p in params):
+        return None  # a trace would freeze whatever the defaults or **kwargs select
+    graph = LeafTracer().trace(parent)
+    gm = fx.GraphModule(parent, graph)
+    mods = dict(parent.named_modules())
+
+    def relu_of(node):
+        if node.kwargs or len(node.args) != 1:
+            return None
+        if node.op == "call_module" and _plain_relu(mods.get(node.target)):
+            return mods[node.target]
+        if node.op == "call_function" and node.target in _RELUS:
+            return F.relu
+        return None
+
+    n_fused = 0
+    for node in list(graph.nodes):
+        if node.op != "call_module" or mods.get(node.target) not in sites or node.kwargs or len(node.args) != 1:
+            continue
+        if len(node.users) != 1:
+            continue
+        site, user = sites[mods[node.target]], next(iter(node.users))
+        last, fused, args = user, None, None
+        if relu_of(user) is not None:
+            fused, args = _Fused(site, relu_of(user)), (node.args[0],)
+        elif (user.op == "call_function" and user.target in _ADDS and not user.kwargs and len(user.args) == 2
+              and all(isinstance(a, fx.Node) for a in user.args) and user.args[0] is not user.args[1] and len(user.users) == 1):
+            last = next(iter(user.users))
+            if relu_of(last) is None:
+                continue
+            bn_first = user.args[0] is node
+            if user.target is operator.iadd and not bn_first:
+                continue  # `other += bn(x)` writes into `other`, which the caller may hold: not the fused call's fresh tensor
+            fused = _Fused(site, relu_of(last), user.target, bn_first)
+            args = (node.args[0], user.args[1] if bn_first else user.args[0])
+        if fused is None:
+            continue
+        name = f"_sl_fused_{n_fused}"
+        n_fused += 1
+        gm.add_submodule(name, fused)
+        with graph.inserting_before(last):
+            new = graph.call_module(name, args)
+        last.replace_all_uses_with(new)
+        graph.erase_node(last)
+        if last is not user:
+            graph.erase_node(user)
+        graph.erase_node(node)
+    if not n_fused:
+        return None
+    graph.lint()
+    gm.recompile()
+    return gm
+
+
+def _owner_forward(parent: nn.Module, gm, training: bool):
+    """The traced forward while the owner is in the mode it was traced in (a trace freezes `if self.training:`), its own otherwise."""
+    own = type(parent).forward
+
+    def forward(*args, **kwargs):
+        if parent.training is training:
+            return gm.forward(*args, **kwargs)
+        return own(parent, *args, **kwargs)
+
+    return forward
+
+
+class _Plan:
+    def __init__(self, model: nn.Module):
+        self.module_ids = tuple(id(m) for m in model.modules())
+        self.sites = {m: _Site(m) for m in model.modules() if _plain_bn(m) and m is not model}
+        self.parents: list = []  # (weak reference to the owner, GraphModule, the owner's training flag when it was traced)
+        for parent in model.modules():
+            if "forward" in parent.__dict__ or not any(child in self.sites for child in parent.children()):
+                continue
+            try:
+                gm = _trace(parent, self.sites)
+            except Exception:  # control flow on tensor values, *args, ...: this module keeps its own forward
+                gm = None
+            if gm is not None:
+                self.parents.append((weakref.ref(parent), gm, parent.training))
+
+    def valid_for(self, model: nn.Module) -> bool:
+        return self.module_ids == tuple(id(m) for m in model.modules())
+
+
+def substitute(model: nn.Module):
+    """Install the fused forwards on ``model``; returns the function that removes them (None when switched off)."""
+    if not enabled() or not isinstance(model, nn.Module):
+        return None
+    plan = _PLANS.get(model)
+    if plan is None or not plan.valid_for(model):
+        plan = _PLANS[model] = _Plan(model)
+    swapped = []
+    for bn, site in plan.sites.items():
+        if "forward" not in bn.__dict__:
+            bn.forward = _bn_forward(site)
+            swapped.append(bn)
+    for ref, gm, training in plan.parents:
+        parent = ref()
+        if parent is not None and "forward" not in parent.__dict__:
+            parent.forward = _owner_forward(parent, gm, training)
+            swapped.append(parent)
+
+    def undo():
+        for m in swapped:
+            m.__dict__.pop("forward", None)
+        swapped.clear()
+
+    return undo

@@ -38,7 +38,7 @@ import torch
 
 from semanticlens_amd import _native as N
 
-from . import aggregators
+from . import _bn_fuse, aggregators
 
 logger = logging.getLogger(__name__)
 
@@ -306,13 +306,21 @@ class ActCache:
     def hook_context(self, model: torch.nn.Module):
         """Register the hooks for the duration of the ``with`` block; always removes them."""
         self._register_hooks(model)
+        undo = None
         try:
+            undo = self._substitute(model)
             yield
         finally:
             for handle in self.handles:
                 handle.remove()
             self.handles.clear()
+            if undo is not None:
+                undo()
             self._finalize()
+
+    def _substitute(self, model: torch.nn.Module):
+        """Forward substitutions that live as long as the hooks; returns the function that undoes them, or None."""
+        return None
 
 
 class ActMaxCache(ActCache):
@@ -374,6 +382,10 @@ class ActMaxCache(ActCache):
             # a forward BOUNDARY (round 6, advisor): groups are planned when the first forward is over — every in-place edit of that
             # forward has bumped its tensor's version by then — and nothing stashed or queued outlives the forward that produced it
             self.handles.append(model.register_forward_hook(self._end_of_forward))
+
+    def _substitute(self, model: torch.nn.Module):
+        # the probed model's inference BatchNorm (+ ReLU, + residual add) on the K16 kernels; undone with the hooks
+        return _bn_fuse.substitute(model)
 
     def _end_of_forward(self, module, ins, outs):
         if self._probe is not None:
