@@ -433,6 +433,31 @@ int sl_batchnorm_infer_add_relu(const float* d_x, const float* d_residual, int64
                                 const float* d_mean, const float* d_var, const float* d_scale, const float* d_bias,
                                 double eps, float* d_y, void* stream);
 
+/* ---- K17: streaming fp32 row top-k — the selection behind label_components / search_components --------
+ * No reference counterpart.  State = d_vals (R,k) fp32 + d_ids (R,k) int64, sorted best-first per row; sl_topk_init writes
+ * the empty slots (value -inf, id -1).  Order: NaN first, then the larger value, -0.0 == +0.0, equal keys by the smaller id; a
+ * real candidate equal to -inf ranks above an empty slot.  The state after a sequence of merges is the top k of everything
+ * seen, whatever the cut into tiles and their order.  1 <= k <= 1024; R == 0 is a no-op. */
+int sl_topk_init(float* d_vals, int64_t* d_ids, int64_t R, int64_t k, void* stream);
+/* Fold a candidate tile into the state: d_cand holds R rows of B >= 1 fp32 columns, row stride ld >= B elements (any 4-byte
+ * aligned start); column j has the id id_base + j, ids stay within [0, 2^62].  The tile is fully consumed when the stream
+ * reaches the end of this call.  d_ws: sl_topk_merge_ws_bytes(R,k,B) bytes (0 for most shapes: few rows of many columns are
+ * split over several wavefronts per row, whose partial selections live there). */
+int sl_topk_merge(float* d_vals, int64_t* d_ids, int64_t R, int64_t k, const float* d_cand, int64_t ld, int64_t B,
+                  int64_t id_base, void* d_ws, size_t ws_bytes, void* stream);
+size_t sl_topk_merge_ws_bytes(int64_t R, int64_t k, int64_t B);
+/* Fold M explicit entries per row — d_other_vals / d_other_ids (R,M), e.g. another state (M = k) or the states of several
+ * layers or ranks side by side — into the state.  Entries with a negative id are empty slots; the caller keeps ids distinct. */
+int sl_topk_merge_states(float* d_vals, int64_t* d_ids, int64_t R, int64_t k, const float* d_other_vals,
+                         const int64_t* d_other_ids, int64_t M, void* stream);
+
+/* normalize(x) @ normalize(y)^T for ANY shapes — x (M,K), y (N,K), out (M,N) — with K6's kernels and arithmetic mode
+ * (sl_set_gemm_mode) and none of similarity_score's shape branches: what the tiled top-k probing calls per tile.
+ * d_ws: sl_cosine_nt_ws_bytes(M,N,K) bytes. */
+int sl_cosine_nt(const float* d_x, int64_t M, const float* d_y, int64_t N, int64_t K, float* d_out, void* d_ws,
+                 size_t ws_bytes, void* stream);
+size_t sl_cosine_nt_ws_bytes(int64_t M, int64_t N, int64_t K);
+
 /* ---- measurement --------------------------------------------------------------------------
  * When enabled, every launch of a profiled kernel family is bracketed by HIP events on its
  * own stream.  sl_prof_read synchronises those events and returns the totals. */
@@ -442,7 +467,8 @@ int sl_batchnorm_infer_add_relu(const float* d_x, const float* d_residual, int64
 #define SL_PROF_GATHER 3
 #define SL_PROF_SCORES 4
 #define SL_PROF_BATCHNORM 5 /* K16 fused inference BatchNorm */
-#define SL_PROF_NFAM 6
+#define SL_PROF_TOPK 6 /* K17 streaming fp32 top-k */
+#define SL_PROF_NFAM 7
 int sl_prof_enable(int on);
 int sl_prof_reset(void);
 /* total_ms: sum of event-bracketed durations; launches: count; bytes: algorithmic bytes

@@ -8,6 +8,7 @@ device, the call raises.  PyTorch is used for device memory and streams only
 from __future__ import annotations
 
 import ctypes
+import operator
 import os
 from pathlib import Path
 
@@ -22,7 +23,7 @@ SL_CONV_MAX, SL_CONV_MEAN, SL_CONV_SUM = 0, 1, 2
 SL_TOK_MEAN, SL_TOK_ABSMEAN, SL_TOK_MAX, SL_TOK_ABSMAX, SL_TOK_TOKEN = 0, 1, 2, 3, 4
 SL_TIES_TOTAL, SL_TIES_ATEN = 0, 1
 SL_MAX_SLOTS = 16
-SL_PROF_REDUCE, SL_PROF_MERGE, SL_PROF_GEMM, SL_PROF_GATHER, SL_PROF_SCORES, SL_PROF_BATCHNORM = 0, 1, 2, 3, 4, 5
+SL_PROF_REDUCE, SL_PROF_MERGE, SL_PROF_GEMM, SL_PROF_GATHER, SL_PROF_SCORES, SL_PROF_BATCHNORM, SL_PROF_TOPK = 0, 1, 2, 3, 4, 5, 6
 SL_ACT_NONE, SL_ACT_GELU, SL_ACT_QUICKGELU, SL_ACT_GELU_TANH = 0, 1, 2, 3
 TIE_MODES = {"total": SL_TIES_TOTAL, "aten": SL_TIES_ATEN}
 SL_PP_PLAN_STRIDE = 16
@@ -112,6 +113,12 @@ SIGNATURES = {
     "sl_heat_boxes": (_int, [_vp, _i64, _i64, _i64, _int, ctypes.c_float, _vp, _vp, _sz, _vp]),
     "sl_batchnorm_infer": (_int, [_vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, ctypes.c_double, _int, _vp, _vp]),
     "sl_batchnorm_infer_add_relu": (_int, [_vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, ctypes.c_double, _vp, _vp]),
+    "sl_topk_init": (_int, [_vp, _vp, _i64, _i64, _vp]),
+    "sl_topk_merge": (_int, [_vp, _vp, _i64, _i64, _vp, _i64, _i64, _i64, _vp, _sz, _vp]),
+    "sl_topk_merge_ws_bytes": (_sz, [_i64, _i64, _i64]),
+    "sl_topk_merge_states": (_int, [_vp, _vp, _i64, _i64, _vp, _vp, _i64, _vp]),
+    "sl_cosine_nt": (_int, [_vp, _i64, _vp, _i64, _i64, _vp, _vp, _sz, _vp]),
+    "sl_cosine_nt_ws_bytes": (_sz, [_i64, _i64, _i64]),
     "sl_prof_enable": (_int, [_int]),
     "sl_prof_reset": (_int, []),
     "sl_prof_read": (_int, [_int, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(_i64), ctypes.POINTER(ctypes.c_double)]),
@@ -798,6 +805,122 @@ def template_mean(E: torch.Tensor, E0: torch.Tensor, Q: int) -> torch.Tensor:
     with _on(Ed.device):
         _check(lib().sl_template_mean(_ptr(Ed), _ptr(E0d), Q, T, D, _ptr(out), _stream(Ed)), "sl_template_mean")
     return out
+
+
+# ------------------------------------------------------------------------------------------------
+# K17: streaming fp32 top-k over cosine tiles
+# ------------------------------------------------------------------------------------------------
+TOPK_MAX_K = 1024
+TOPK_TILE_BYTES = 128 << 20  # the similarity tile one GEMM writes and one merge reads
+
+
+def check_topk_k(k) -> int:
+    try:
+        k = operator.index(k)  # any integral type (numpy.int64 included); floats and strings are refused
+    except TypeError:
+        raise ValueError(f"k must be an integer, got {k!r}") from None
+    if k < 1 or k > TOPK_MAX_K:
+        raise ValueError(f"k = {k} not in [1, {TOPK_MAX_K}]")
+    return k
+
+
+def topk_init(vals: torch.Tensor, ids: torch.Tensor):
+    """Empty ``(R, k)`` state: values -inf, ids -1."""
+    R, k = vals.shape
+    with _on(vals.device):
+        _check(lib().sl_topk_init(_ptr(vals), _ptr(ids), R, k, _stream(vals)), "sl_topk_init")
+
+
+def topk_new(R: int, k: int, device) -> tuple[torch.Tensor, torch.Tensor]:
+    vals = torch.empty((R, k), dtype=torch.float32, device=device)
+    ids = torch.empty((R, k), dtype=torch.int64, device=device)
+    topk_init(vals, ids)
+    return vals, ids
+
+
+def topk_merge(vals: torch.Tensor, ids: torch.Tensor, cand: torch.Tensor, id_base: int = 0, ws: torch.Tensor | None = None):
+    """Fold the ``(R, B)`` fp32 tile ``cand`` (unit column stride, any row stride) into the state; column ``j`` has the id
+    ``id_base + j``.  ``ws``: a uint8 device buffer to use as the workspace of a split row when it is large enough."""
+    R, k = vals.shape
+    if cand.ndim != 2 or cand.shape[0] != R or cand.dtype != torch.float32 or not cand.is_cuda:
+        raise ValueError(f"topk_merge: candidate tile {tuple(cand.shape)} {cand.dtype} does not fit a state of {R} rows")
+    B = cand.shape[1]
+    if B > 1 and cand.stride(1) != 1:
+        cand = cand.contiguous()
+    ld = cand.stride(0) if R > 1 else B
+    if ld < B:
+        cand, ld = cand.contiguous(), B
+    nbytes = int(lib().sl_topk_merge_ws_bytes(R, k, B))
+    if nbytes and (ws is None or ws.numel() < nbytes):
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=vals.device)
+    with _on(vals.device):
+        rc = lib().sl_topk_merge(_ptr(vals), _ptr(ids), R, k, _ptr(cand), ld, B, id_base, _ptr(ws), nbytes, _stream(vals))
+    _check(rc, "sl_topk_merge")
+
+
+def topk_merge_states(vals: torch.Tensor, ids: torch.Tensor, other_vals: torch.Tensor, other_ids: torch.Tensor):
+    """Fold ``(R, M)`` explicit (value, id) entries into the state (negative ids are empty slots)."""
+    R, k = vals.shape
+    if other_vals.shape != other_ids.shape or other_vals.ndim != 2 or other_vals.shape[0] != R:
+        raise ValueError(f"topk_merge_states: entries {tuple(other_vals.shape)} / {tuple(other_ids.shape)} do not fit {R} rows")
+    ov = other_vals.to(torch.float32).contiguous()
+    oi = other_ids.to(torch.int64).contiguous()
+    with _on(vals.device):
+        rc = lib().sl_topk_merge_states(_ptr(vals), _ptr(ids), R, k, _ptr(ov), _ptr(oi), ov.shape[1], _stream(vals))
+    _check(rc, "sl_topk_merge_states")
+
+
+def cosine_nt(x: torch.Tensor, y: torch.Tensor, out: torch.Tensor, ws: torch.Tensor | None = None) -> torch.Tensor:
+    """``out[:] = normalize(x) @ normalize(y).T`` for contiguous fp32 device tensors of any shapes (K6's kernels, without
+    ``similarity_score``'s shape branches)."""
+    M, K = x.shape
+    Nn = y.shape[0]
+    nbytes = int(lib().sl_cosine_nt_ws_bytes(M, Nn, K))
+    if ws is None or ws.numel() < nbytes:
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
+    with _on(x.device):
+        rc = lib().sl_cosine_nt(_ptr(x), M, _ptr(y), Nn, K, _ptr(out), _ptr(ws), ws.numel(), _stream(x))
+    _check(rc, "sl_cosine_nt")
+    return out
+
+
+def topk_chunk_rows(R: int, n_cols: int, tile_bytes: int = TOPK_TILE_BYTES) -> int:
+    """Columns per tile so that an ``(R, chunk)`` fp32 tile stays at or under ``tile_bytes``."""
+    return max(1, min(n_cols, tile_bytes // (4 * max(R, 1))))
+
+
+def topk_probe(x: torch.Tensor, y: torch.Tensor, k: int, chunk_rows: int | None = None, id_base: int = 0, state=None):
+    """Per row of ``x (R, D)``: the ``k`` largest cosines against the rows of ``y (N, D)`` (row ``j`` has the id
+    ``id_base + j``), as ``(values (R, k) float32, ids (R, k) int64)``.
+
+    Always ``normalize(x) @ normalize(y).T`` — none of ``similarity_score``'s shape branches apply.  The cosine GEMM (K6, in
+    the arithmetic ``set_gemm_mode`` selects) writes one reused ``(R, chunk_rows)`` tile at a time and K17 folds it into the
+    state on the same stream, so the ``(R, N)`` matrix never exists.  ``state``: continue an existing ``(values, ids)`` pair."""
+    k = check_topk_k(k)
+    if x.ndim != 2 or y.ndim != 2:
+        raise ValueError("topk_probe expects 2-D tensors")
+    if y.shape[1] != x.shape[1]:
+        raise ValueError(f"embedding widths differ: {x.shape[1]} vs {y.shape[1]}")
+    if chunk_rows is not None and chunk_rows < 1:
+        raise ValueError(f"chunk_rows = {chunk_rows} must be at least 1")
+    xd = _f32c(x)
+    yd = _f32c(y, xd.device)
+    R, n = xd.shape[0], yd.shape[0]
+    vals, ids = state if state is not None else topk_new(R, k, xd.device)
+    if R == 0 or n == 0:
+        return vals, ids
+    step = min(chunk_rows or topk_chunk_rows(R, n), n)
+    tile = torch.empty(R * step, dtype=torch.float32, device=xd.device)
+    ws = torch.empty(int(lib().sl_cosine_nt_ws_bytes(R, step, xd.shape[1])), dtype=torch.uint8, device=xd.device)
+    # the split-row workspace is largest for the widest tile (the waves per row grow with the columns), so one buffer serves all
+    merge_bytes = int(lib().sl_topk_merge_ws_bytes(R, k, step))
+    merge_ws = torch.empty(merge_bytes, dtype=torch.uint8, device=xd.device) if merge_bytes else None
+    for start in range(0, n, step):
+        rows = min(step, n - start)
+        out = tile[: R * rows].view(R, rows)
+        cosine_nt(xd, yd[start : start + rows], out, ws)
+        topk_merge(vals, ids, out, id_base + start, merge_ws)
+    return vals, ids
 
 
 # ------------------------------------------------------------------------------------------------

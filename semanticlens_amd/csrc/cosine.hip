@@ -529,6 +529,24 @@ SL_API int sl_similarity_multi(const float* d_x, int64_t Q, int64_t K, const flo
   return cosine_matrix_multi(d_x, Q, K, h_d_ys, h_Cs, L, h_d_outs, ws, (hipStream_t)stream);
 }
 
+SL_API size_t sl_cosine_nt_ws_bytes(int64_t M, int64_t N, int64_t K) {
+  if (M < 0 || N < 0 || K < 0) return 0;
+  return align256((size_t)M * 4) + align256((size_t)N * 4) + cosine_split_bytes(M, N, K) + 256;
+}
+
+SL_API int sl_cosine_nt(const float* d_x, int64_t M, const float* d_y, int64_t N, int64_t K, float* d_out, void* d_ws,
+                        size_t ws_bytes, void* stream) {
+  SL_REQUIRE(M >= 0 && N >= 0 && K >= 0, "sl_cosine_nt: negative shape");
+  if (M * N == 0) return 0;
+  SL_REQUIRE(d_x && d_y && d_out, "sl_cosine_nt: null pointer");
+  SL_REQUIRE(d_ws && ws_bytes >= sl_cosine_nt_ws_bytes(M, N, K), "sl_cosine_nt: workspace too small");
+  unsigned char* ws = (unsigned char*)(((uintptr_t)d_ws + 255) & ~(uintptr_t)255);
+  float* rx = (float*)ws;
+  float* ry = (float*)(ws + align256((size_t)M * 4));
+  void* split = ws + align256((size_t)M * 4) + align256((size_t)N * 4);
+  return cosine_matrix_nt(d_x, M, d_y, N, K, rx, ry, d_out, split, (hipStream_t)stream);
+}
+
 SL_API int sl_set_gemm_mode(int mode) {
   SL_REQUIRE(mode >= -1 && mode <= 1, "sl_set_gemm_mode: mode %d not in {-1 (environment), 0 (f32), 1 (bf16x3)}", mode);
   set_gemm_mode(mode);

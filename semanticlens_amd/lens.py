@@ -137,6 +137,166 @@ def _probe(query: torch.Tensor, aggregated_concept_db):
     return {key: similarity_score(query.to(value.device), value) for key, value in aggregated_concept_db.items()}
 
 
+# ------------------------------------------------------------------------------------------------
+# describe / search: top-k cosine without the full matrix (K6 tiles + K17 selection)
+# ------------------------------------------------------------------------------------------------
+LABEL_CHUNK_WORDS = 8192  # vocabulary words embedded and probed at a time when ``chunk_size`` is not given
+
+
+def _db_layers(aggregated_concept_db):
+    """``(names, tensors, is_dict)`` of a ``(C, D)`` tensor or a dict of them; shape errors raise before the device is touched."""
+    is_dict = not isinstance(aggregated_concept_db, torch.Tensor)
+    names = list(aggregated_concept_db) if is_dict else [None]
+    layers = [aggregated_concept_db[n] for n in names] if is_dict else [aggregated_concept_db]
+    for name, layer in zip(names, layers):
+        if not isinstance(layer, torch.Tensor) or layer.ndim != 2:
+            what = f"layer {name!r}" if is_dict else "the concept DB"
+            raise ValueError(f"{what} must be a 2-D (n_components, D) tensor, got {tuple(getattr(layer, 'shape', ()))}")
+    widths = {layer.shape[1] for layer in layers}
+    if len(widths) > 1:
+        raise ValueError(f"the layers' embedding widths differ: {sorted(widths)}")
+    return names, layers, is_dict
+
+
+def _check_width(embeds: torch.Tensor, layers):
+    if embeds.ndim != 2:
+        raise ValueError(f"query embeddings must be 2-D (n, D), got {tuple(embeds.shape)}")
+    if layers and embeds.shape[1] != layers[0].shape[1]:
+        raise ValueError(f"embedding width {embeds.shape[1]} does not match the concept DB's {layers[0].shape[1]}")
+
+
+@torch.no_grad()
+def _embed_words(fm, words: list[str], templates: list[str] | None, batch_size: int | None, empty=None) -> torch.Tensor:
+    """``(len(words), D)`` text embeddings; with templates, each word's mean over ITS OWN templates minus the empty-template
+    embedding.  The templated list is built query-major (``for w in words for t in templates``), the grouping
+    ``N.template_mean`` reads (``E[(q * T + t) * D + d]``) — unlike ``_embed_text_probes``, whose template-major list regrouped
+    query-major mixes the queries of one call (kept there because the reference does it).  ``empty``: the ``(T, D)``
+    empty-template embeddings when the caller already has them."""
+    if not templates:
+        return _encode_texts(fm, words, batch_size)
+    templated = _encode_texts(fm, [t.format(w) for w in words for t in templates], batch_size)
+    if empty is None:
+        empty = fm.encode_text(fm.tokenize([t.format("") for t in templates]).to(fm.device))
+    return N.template_mean(templated, empty, len(words))
+
+
+def _decode_layers(ids: torch.Tensor, sizes: list[int]):
+    """Global component ids (``offset[layer] + component``; -1 = empty slot) -> ``(layer_index, component)``."""
+    ends = torch.tensor(sizes, dtype=torch.int64, device=ids.device).cumsum(0)
+    layer = torch.bucketize(ids, ends, right=True)
+    component = ids - (ends - torch.tensor(sizes, dtype=torch.int64, device=ids.device))[layer.clamp(max=len(sizes) - 1)]
+    empty = ids < 0
+    return layer.masked_fill(empty, -1), component.masked_fill(empty, -1)
+
+
+@torch.no_grad()
+def probe_topk(query_embeds: torch.Tensor, aggregated_concept_db, k: int, per: str = "component", chunk_rows: int | None = None):
+    """Top-``k`` cosine between ``query_embeds (Q, D)`` and a concept DB (a ``(C, D)`` tensor or a dict of layers), for
+    callers who bring their own vectors (an image vocabulary, say).  The ``(Q, C)`` matrix is never formed: the cosine GEMM
+    writes one tile at a time and the streaming fp32 top-k (K17) folds it into a ``(rows, k)`` state.
+
+    * ``per="component"``: for every component its best queries — ``(values (C, k) float32, ids (C, k) int64)`` with ``ids``
+      indexing ``query_embeds``, or a dict of such pairs for a dict DB.
+    * ``per="query"``: for every query its best components ACROSS all layers — ``(values (Q, k), layer_index (Q, k),
+      component (Q, k), layer_names)``; per layer a top-k over the layer's components under the global id
+      ``offset[layer] + component``, then a merge of the layers' states.  ``layer_names`` is ``[None]`` for a tensor DB.
+
+    Order: larger cosine first, NaN before every number, equal cosines by the smaller id.  Slots beyond the number of
+    candidates hold ``-inf`` / ``-1``.  Always ``normalize(x) @ normalize(y).T``: none of ``similarity_score``'s shape
+    branches apply.  Results live on the DB's device (its first layer's for ``per="query"``)."""
+    k = N.check_topk_k(k)
+    if per not in ("component", "query"):
+        raise ValueError(f'per must be "component" or "query", got {per!r}')
+    names, layers, is_dict = _db_layers(aggregated_concept_db)
+    _check_width(query_embeds, layers)
+    if per == "component":
+        out = {}
+        q = None
+        for name, layer in zip(names, layers):
+            ld = N._f32c(layer)
+            q = N._f32c(query_embeds, ld.device) if q is None or q.device != ld.device else q
+            vals, ids = N.topk_probe(ld, q, k, chunk_rows)
+            out[name] = (vals.to(layer.device), ids.to(layer.device))
+        return out if is_dict else out[None]
+    q = N._f32c(query_embeds)
+    vals, ids = N.topk_new(q.shape[0], k, q.device)
+    offset = 0
+    for layer in layers:
+        lv, li = N.topk_probe(q, N._f32c(layer, q.device), k, chunk_rows, id_base=offset)
+        N.topk_merge_states(vals, ids, lv, li)
+        offset += layer.shape[0]
+    layer_index, component = _decode_layers(ids, [layer.shape[0] for layer in layers])
+    dev = layers[0].device if layers else query_embeds.device
+    return vals.to(dev), layer_index.to(dev), component.to(dev), names
+
+
+@torch.no_grad()
+def label_components(fm, vocabulary: list[str], aggregated_concept_db, k: int = 5, templates: list[str] | None = None,
+                     batch_size: int | None = None, chunk_size: int | None = None):
+    """For every component, its ``k`` best labels out of ``vocabulary``: ``(values (C, k) float32, ids (C, k) int64)`` for a
+    ``(C, D)`` tensor, a dict of such pairs for a dict of layers, on the DB's device; ``ids`` index ``vocabulary``.
+
+    The vocabulary is embedded ``chunk_size`` words at a time (default ``LABEL_CHUNK_WORDS``; ``batch_size`` is the text
+    tower's batch, as in ``text_probing``), each chunk goes through one cosine GEMM per layer — the DB as rows, the chunk as
+    columns — and is folded into the layers' top-k states.  Neither the ``V x C`` similarity matrix nor, for
+    ``chunk_size < V``, all ``V x D`` embeddings are ever resident.
+
+    Templates: each word's embedding is the mean over ITS OWN templated prompts minus the empty-template embedding.
+    ``text_probing`` instead reproduces the reference's regrouping, which mixes the queries of one call and so depends on
+    the whole list; that cannot survive chunking and is deliberately not reproduced here (for a single query the two
+    agree).  With ``templates=None`` a word's embedding is exactly ``fm.encode_text(fm.tokenize([w]))``'s row.
+
+    ``k``, the vocabulary, ``chunk_size`` and the DB's shape are checked before anything runs.  The text tower's width is
+    not known until it has produced an embedding, so a ``D`` mismatch raises ``ValueError`` only after the first chunk has
+    been embedded (and the DB has been moved to the device); nothing has been multiplied by then."""
+    k = N.check_topk_k(k)
+    if isinstance(vocabulary, str) or not isinstance(vocabulary, (list, tuple)) or len(vocabulary) == 0:
+        raise ValueError("vocabulary must be a non-empty list of strings")
+    if chunk_size is not None and chunk_size < 1:
+        raise ValueError(f"chunk_size = {chunk_size} must be at least 1")
+    names, layers, is_dict = _db_layers(aggregated_concept_db)
+    vocabulary = list(vocabulary)
+    dbs = [N._f32c(layer) for layer in layers]  # raises without a HIP device, before the text tower runs
+    states = [None] * len(dbs)
+    step = chunk_size or LABEL_CHUNK_WORDS
+    empty = None
+    if templates:
+        empty = fm.encode_text(fm.tokenize([t.format("") for t in templates]).to(fm.device))
+    for start in range(0, len(vocabulary), step):
+        embeds = _embed_words(fm, vocabulary[start : start + step], templates, batch_size, empty)
+        _check_width(embeds, layers)
+        for i, db in enumerate(dbs):
+            states[i] = N.topk_probe(db, embeds, k, id_base=start, state=states[i])
+    out = {name: (vals.to(layer.device), ids.to(layer.device)) for name, layer, (vals, ids) in zip(names, layers, states)}
+    return out if is_dict else out[None]
+
+
+@torch.no_grad()
+def search_components(fm, query, aggregated_concept_db, k: int = 10, templates: list[str] | None = None,
+                      batch_size: int | None = None):
+    """The ``k`` components that best match each text query across ALL layers: ``(values (Q, k), layer_index (Q, k),
+    component (Q, k), layer_names)`` (see ``probe_topk(per="query")``).  Templates are applied per query, as in
+    ``label_components``; as there, a ``D`` mismatch can only raise once the text tower has embedded the queries."""
+    k = N.check_topk_k(k)
+    queries = list(query) if isinstance(query, (list, tuple)) else [query]
+    if not queries:
+        raise ValueError("search_components needs at least one query")
+    _, layers, _ = _db_layers(aggregated_concept_db)
+    for layer in layers:
+        N._f32c(layer)  # raises without a HIP device, before the text tower runs
+    return probe_topk(_embed_words(fm, queries, templates, batch_size), aggregated_concept_db, k, per="query")
+
+
+@torch.no_grad()
+def search_components_image(fm, query, aggregated_concept_db, k: int = 10):
+    """``search_components`` for an image query (several images are averaged, as in ``image_probing``): one result row.
+    ``k`` and the DB's shape are checked first; the image tower's width is only known from its output, so a ``D`` mismatch
+    raises ``ValueError`` after the tower has run and before any similarity is computed."""
+    k = N.check_topk_k(k)
+    _db_layers(aggregated_concept_db)
+    return probe_topk(_embed_image_probe(fm, query), aggregated_concept_db, k, per="query")
+
+
 class Lens:
     """Holds the foundation model and wraps the workflow (reference: lens.py:217-480)."""
 
@@ -185,6 +345,15 @@ class Lens:
 
     def image_probing(self, query, aggregated_concept_db):
         return image_probing(self.fm, query, aggregated_concept_db)
+
+    def label_components(self, vocabulary, aggregated_concept_db, k=5, templates=None, batch_size=None, chunk_size=None):
+        return label_components(self.fm, vocabulary, aggregated_concept_db, k, templates, batch_size, chunk_size)
+
+    def search_components(self, query, aggregated_concept_db, k=10, templates=None, batch_size=None):
+        return search_components(self.fm, query, aggregated_concept_db, k, templates, batch_size)
+
+    def search_components_image(self, query, aggregated_concept_db, k=10):
+        return search_components_image(self.fm, query, aggregated_concept_db, k)
 
     @staticmethod
     def _per_layer(fn, db):
