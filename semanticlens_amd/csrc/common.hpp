@@ -91,10 +91,6 @@ __host__ __device__ inline uint16_t f32_to_bf16_rne(float f) {
 }
 __host__ __device__ inline float bf16_to_f32(uint16_t h) { return bits_f32((uint32_t)h << 16); }
 
-// fp32 -> fp16 RNE and back (for activations that arrive in half precision: the reference
-// aggregates in the tensor's dtype before the bf16 cast).
-__device__ inline float round_through_f16(float f) { return (float)(_Float16)f; }
-
 // Monotone 16-bit key of a bf16 bit pattern for "value descending" compares that match
 // ATen's comparator `(isnan(a) && !isnan(b)) || a > b` (TopKImpl.h): NaN is the largest,
 // -0.0 == +0.0, larger key == larger value.

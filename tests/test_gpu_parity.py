@@ -422,6 +422,84 @@ def test_conv_reduce_fp32_dma_ring_unaligned_long_windows(shape):
             assert np.array_equal(got[~fin & ~np.isnan(want)], want[~fin & ~np.isnan(want)]), (shape, name)
 
 
+# One case per (G, U) call site of rowreduce_dma that the dispatch ladders can reach (reduce_row.hip dispatch_rowreduce_t,
+# reduce_row_half.hip dispatch_rowreduce_h_t): the smallest (B, C, H, W) of >= 8 MiB whose R = B * C has exactly the
+# divisibility the site's guard asks for and whose S = H * W puts a task at the wanted number of tasks per batch U.
+DMA_SITES_F32 = [
+    ("G4 aligned U4", (128, 1024, 4, 4)),        # S = 16, R % 16 == 0
+    ("G8 aligned U4", (8, 16385, 4, 4)),         # S = 16, R % 16 == 8
+    ("G16 aligned U4 (one step)", (4, 32769, 4, 4)),  # S = 16, R % 8 == 4
+    ("G32 aligned U4", (2, 65537, 4, 4)),        # S = 16, R % 4 == 2
+    ("G64 aligned U4", (3, 43691, 4, 4)),        # S = 16, R odd
+    ("G16 aligned U1", (8, 1024, 16, 16)), ("G16 aligned U2", (16, 1024, 8, 16)),
+    ("G16 aligned U3", (8, 3277, 8, 10)), ("G16 aligned U4", (32, 1024, 8, 8)),
+    ("G64 long U3", (2, 4033, 13, 20)), ("G64 long U2", (7, 871, 8, 43)), ("G64 long U1", (5, 813, 12, 43)),
+    ("G4 unaligned U4", (64, 3641, 3, 3)), ("G8 unaligned U4", (8, 10486, 5, 5)), ("G16 unaligned U4", (4, 10700, 7, 7)),
+    ("G32 multi U2", (2, 8323, 9, 14)), ("G32 multi U1", (2, 4065, 6, 43)),
+    ("G16 multi U2", (4, 8323, 7, 9)), ("G16 multi U1", (4, 4065, 3, 43)),
+]
+DMA_SITES_HALF = [
+    ("G16 aligned U1", (8, 1024, 16, 32)), ("G16 aligned U2", (16, 1024, 16, 16)),
+    ("G16 aligned U3", (8, 3277, 10, 16)), ("G16 aligned U4", (32, 1024, 8, 16)),
+    ("G4 aligned U4", (512, 1024, 2, 4)),
+    ("G64 long U3", (2, 4033, 13, 40)), ("G64 long U2", (7, 871, 16, 43)), ("G64 long U1", (5, 813, 24, 43)),
+    ("G4 unaligned U4", (64, 7282, 3, 3)), ("G8 unaligned U4", (8, 10700, 7, 7)), ("G16 unaligned U4", (4, 11651, 9, 10)),
+    ("G32 unaligned U4", (2, 10700, 14, 14)),
+    ("G32 multi U2", (2, 8323, 14, 18)), ("G32 multi U1", (2, 4065, 12, 43)), ("G32 multi 16K", (2, 2041, 4, 257)),
+    ("G16 multi U2", (4, 8595, 2, 61)), ("G16 multi U1", (4, 4065, 6, 43)), ("G16 multi 16K", (4, 2041, 2, 257)),
+    ("G8 multi U2", (8, 8323, 7, 9)), ("G8 multi U1", (8, 4065, 3, 43)), ("G8 multi 16K", (8, 2041, 1, 257)),
+]
+DMA_SITE_CASES = ([(torch.float32, s, n) for n, s in DMA_SITES_F32] +
+                  [(dt, s, n) for dt in (torch.float16, torch.bfloat16) for n, s in DMA_SITES_HALF])
+
+
+@pytest.mark.parametrize("dt,shape,site", DMA_SITE_CASES, ids=[f"{str(d)[6:]}-{n.replace(' ', '_')}" for d, _, n in DMA_SITE_CASES])
+def test_conv_reduce_dma_every_reachable_site(dt, shape, site):
+    """Every surviving `rowreduce_dma_kernel` call site, fp32 and half: the ladders instantiate only the U values their guards
+    allow and report any other as an internal error, so each case asserts that the entry point returned 0.  Compared like
+    test_conv_reduce_vs_oracle (max exact, mean rtol 2e-6 / atol 1e-6 and <= 1 bf16 ulp on the candidate); for fp16 / bf16 the
+    mean is rounded once to the activation dtype, where fp32 summation order can move it by one ulp of that dtype (2^-10 /
+    2^-7), the bound of the half-precision tests above.  NaN at a row's first and at a row's last element.  Values are
+    N(2, 1): among the 10^5 rows of these shapes some N(0, 1) rows have a mean near zero, where a bf16 ulp of the mean is smaller
+    than the fp32 tolerance and the ulp comparison says nothing about the kernel."""
+    B, C, H, W = shape
+    es = 4 if dt == torch.float32 else 2
+    assert B * C * H * W * es >= 8 << 20
+    g = torch.Generator().manual_seed(sum(shape))
+    x = (torch.randn(*shape, generator=g) + 2.0).to(dt)
+    x[0, 0, 0, 0] = float("nan")  # a row's first element
+    x[-1, -1, -1, -1] = float("nan")  # a row's last element (the tensor's last)
+    x[B // 2, C // 2, 0, 0] = float("nan")
+    x[B // 2, C // 2 - 1, -1, -1] = float("nan")
+    x[-1, 1].fill_(-3.0)
+    x[-1, 1, -1, -1] = float("inf")
+    xd = x.to(DEV)
+    xf = x.float().numpy()
+    flat, sb, sc, ss = N._flatten_spatial(xd)
+    for name, code in (("max", N.SL_CONV_MAX), ("mean", N.SL_CONV_MEAN)):
+        cand = torch.empty((B, C), dtype=torch.bfloat16, device=DEV)
+        out = torch.empty((B, C), dtype=torch.float32, device=DEV)
+        with N._on(xd.device):
+            rc = N.lib().sl_reduce_conv(N._ptr(flat), N._dtype_code(flat), B, C, H * W, sb, sc, ss, code, N._ptr(cand), N._ptr(out),
+                                        N._stream(flat))
+        assert rc == 0, (site, rc, N.lib().sl_last_error())
+        want = oracle.agg_conv(xf, name)
+        if name == "max":
+            assert feq(out.cpu().numpy(), want), site  # exact
+            assert np.array_equal(bits(cand), oracle.f32_to_bf16(want)), site
+        elif dt == torch.float32:
+            np.testing.assert_allclose(out.cpu().numpy(), want, rtol=2e-6, atol=1e-6, equal_nan=True)
+            d = np.abs(bits(cand).astype(np.int32) - oracle.f32_to_bf16(want).astype(np.int32))
+            assert d.max() <= 1, site  # <= 1 bf16 ulp
+        else:
+            want = torch.from_numpy(want).to(dt).float().numpy()
+            got = out.cpu().numpy()
+            np.testing.assert_allclose(got, want, rtol=2.0 ** -10 if dt == torch.float16 else 2.0 ** -7, atol=1e-6, equal_nan=True)
+            assert np.array_equal(bits(cand), oracle.f32_to_bf16(got)), site  # the candidate is the bf16 cast of that output
+            d = np.abs(bits(cand).astype(np.int32) - oracle.f32_to_bf16(want).astype(np.int32))
+            assert d.max() <= 1, site  # <= 1 bf16 ulp (an ulp of fp16 or bf16 is at most one of bf16)
+
+
 @pytest.mark.parametrize("dt", [torch.float16, torch.bfloat16])
 def test_half_precision_full_size_equals_torch(dt):
     """ResNet-50 layer shapes at the bench batch size: the kernels' max equals torch.amax bit for bit in both layouts."""

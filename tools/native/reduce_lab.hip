@@ -4,10 +4,14 @@
 //                         the same stream right before every reduce; the reduce's own dispatch time comes from sl_prof;
 //                         sweeps sl_set_reduce_policy(nt_min_bytes, tail_bytes)
 //   reduce_lab pipe1      the same with the SHIPPED policy only (48 launches per shape): the run to put under rocprofv3
-// Build: tools/native/build_reduce_lab.sh [-DSL_REDUCE_LAB=n] [-DSL_REDUCE_LAB_HEAD_AUX=a -DSL_REDUCE_LAB_TAIL_AUX=b -DSL_REDUCE_LAB_TAIL_FIRST=1]
-#include "../../semanticlens_amd/csrc/reduce.hip"
+// Calls nothing but the public ABI and links the built library.  Build: tools/native/build_reduce_lab.sh
+#include <hip/hip_ext.h>
+#include <hip/hip_runtime.h>
+
+#include "../../include/semanticlens_amd.h"
 
 #include <algorithm>
+#include <cstdint>
 #include <cstdio>
 #include <cstring>
 #include <vector>
