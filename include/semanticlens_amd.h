@@ -68,7 +68,7 @@ int sl_abi_version(void);
 /* Variant switches — which of several BIT-IDENTICAL kernel variants a dispatcher picks (0 = its own rule).  The parity tests walk the
  * variants with these; production code never needs them.  Names: "g3_tile" (split-bf16 GEMM tile: 128, 256, 8, 160, 64, 1280),
  * "f32_tile" (fp32-MFMA GEMM: 128, 8), "g3_strip_off" (1: no column-strip split), "colreduce_nw" (K2 waves per task: 4, 8, 16),
- * "bn_policy" (K16 cache policy: 1 plain, 2 non-temporal stores, 3 non-temporal loads and stores).
+ * "bn_policy" (K16 cache policy: 1 plain, 2 non-temporal stores, 3 non-temporal loads and stores; 0: 3 from 206 MB, else 1).
  * The environment variable SL_OPTIONS="name=value,..." presets them for a process; an explicit call wins.  No reference counterpart. */
 int sl_set_option(const char* name, int64_t value);
 int64_t sl_get_option(const char* name); /* -1 for an unknown name */
@@ -432,6 +432,13 @@ int sl_batchnorm_infer(const float* d_x, int64_t B, int64_t C, int64_t HW, const
 int sl_batchnorm_infer_add_relu(const float* d_x, const float* d_residual, int64_t B, int64_t C, int64_t HW,
                                 const float* d_mean, const float* d_var, const float* d_scale, const float* d_bias,
                                 double eps, float* d_y, void* stream);
+/* K18: max_pool2d(clamp_min(y, 0), (kh,kw), (sh,sw), (ph,pw)) of the same y in one pass, bit for bit what ATen's
+ * max-pool writes (window clipped to the input, row-major scan, the last NaN of a window wins); no indices, no ceil_mode,
+ * dilation 1.  d_x (B,C,H,W), d_y (B,C,OH,OW) with OH = (H + 2 ph - kh) / sh + 1.  k in {2,3}, s in {1,2}, p <= k / 2 per axis,
+ * W <= 4096; anything else is SL_E_INVALID. */
+int sl_batchnorm_infer_relu_maxpool(const float* d_x, int64_t B, int64_t C, int64_t H, int64_t W, const float* d_mean,
+                                    const float* d_var, const float* d_scale, const float* d_bias, double eps, int kh, int kw,
+                                    int sh, int sw, int ph, int pw, float* d_y, void* stream);
 
 /* ---- K17: streaming fp32 row top-k — the selection behind label_components / search_components --------
  * No reference counterpart.  State = d_vals (R,k) fp32 + d_ids (R,k) int64, sorted best-first per row; sl_topk_init writes

@@ -113,6 +113,8 @@ SIGNATURES = {
     "sl_heat_boxes": (_int, [_vp, _i64, _i64, _i64, _int, ctypes.c_float, _vp, _vp, _sz, _vp]),
     "sl_batchnorm_infer": (_int, [_vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, ctypes.c_double, _int, _vp, _vp]),
     "sl_batchnorm_infer_add_relu": (_int, [_vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, ctypes.c_double, _vp, _vp]),
+    "sl_batchnorm_infer_relu_maxpool": (_int, [_vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, ctypes.c_double, _int, _int, _int,
+                                               _int, _int, _int, _vp, _vp]),
     "sl_topk_init": (_int, [_vp, _vp, _i64, _i64, _vp]),
     "sl_topk_merge": (_int, [_vp, _vp, _i64, _i64, _vp, _i64, _i64, _i64, _vp, _sz, _vp]),
     "sl_topk_merge_ws_bytes": (_sz, [_i64, _i64, _i64]),
@@ -946,6 +948,31 @@ def batchnorm_infer(x: torch.Tensor, mean: torch.Tensor, var: torch.Tensor, weig
             rc = lib().sl_batchnorm_infer_add_relu(_ptr(x), _ptr(residual), B, C, H * W, _ptr(mean), _ptr(var), _ptr(weight),
                                                    _ptr(bias), float(eps), _ptr(out), _stream(x))
     _check(rc, "sl_batchnorm_infer")
+    return out
+
+
+BN_POOL_MAX_WIDTH = 4096
+BN_POOL_STAGE_BYTES = 64 * 1024  # a plane with more bytes of rows than this is pooled in bands of rows
+
+
+def bn_pool_supported(kernel_size, stride, padding) -> bool:
+    """Whether ``sl_batchnorm_infer_relu_maxpool`` takes these per-axis (h, w) pool parameters."""
+    return all(k in (2, 3) and s in (1, 2) and 0 <= p <= k // 2 for k, s, p in zip(kernel_size, stride, padding))
+
+
+def batchnorm_infer_relu_maxpool(x: torch.Tensor, mean: torch.Tensor, var: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor,
+                                 eps: float, kernel_size, stride, padding) -> torch.Tensor:
+    """``F.max_pool2d(relu_(F.batch_norm(x, ..., training=False)), kernel_size, stride, padding)`` of a contiguous NCHW fp32 device
+    tensor in one pass, bit for bit (K18).  ``kernel_size``, ``stride`` and ``padding`` are (h, w) pairs; the library refuses
+    what ``bn_pool_supported`` does not list."""
+    B, C, H, W = x.shape
+    (kh, kw), (sh, sw), (ph, pw) = kernel_size, stride, padding
+    oh, ow = ((n + 2 * p - k) // s + 1 if s > 0 else 0 for n, k, s, p in ((H, kh, sh, ph), (W, kw, sw, pw)))
+    out = torch.empty((B, C, max(oh, 0), max(ow, 0)), dtype=x.dtype, device=x.device)
+    with _on(x.device):
+        rc = lib().sl_batchnorm_infer_relu_maxpool(_ptr(x), B, C, H, W, _ptr(mean), _ptr(var), _ptr(weight), _ptr(bias),
+                                                   float(eps), kh, kw, sh, sw, ph, pw, _ptr(out), _stream(x))
+    _check(rc, "sl_batchnorm_infer_relu_maxpool")
     return out
 
 

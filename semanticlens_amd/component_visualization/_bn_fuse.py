@@ -6,12 +6,15 @@ the model is touched and outside the ``with`` block of :meth:`ActCache.hook_cont
 * Every plain ``BatchNorm2d`` gets a ``forward`` that calls ``sl_batchnorm_infer`` when the call is eligible and the class's
   own ``forward`` otherwise.  The module is still *called*, so its hooks fire as before.
 * Every module that directly owns a ``BatchNorm2d`` is traced with ``torch.fx`` — all of its children are leaves, so they are
-  still called as modules and their hooks fire — and the patterns ``bn -> relu`` and ``bn -> add(., other) -> relu`` are replaced
-  by one fused call each.  A module that does not trace keeps its own ``forward``.
+  still called as modules and their hooks fire — and the patterns ``bn -> relu``, ``bn -> add(., other) -> relu`` and
+  ``bn -> relu -> max_pool2d`` (the stem) are replaced by one fused call each.  A module that does not trace
+  keeps its own ``forward``.
 
 Eligibility is decided per call (``_eligible``): eval mode with running statistics and affine parameters, fp32 on a HIP device,
 NCHW-contiguous, grad mode off, MIOpen enabled, and for the fused patterns no hook on the norm or the activation, whose separate
-outputs disappear.  Anything else runs the modules as the user wrote them.
+outputs disappear.  The pooled form also needs pool parameters the kernel takes (read from the module at every call), no
+``ceil_mode`` or ``return_indices`` and no hook on the pool; otherwise it falls back one level, to the fused ``bn -> relu`` and
+the user's pool module.  Anything else runs the modules as the user wrote them.
 
 Proof before trust: the first time a site runs an epilogue, the same input also goes through ``F.batch_norm`` (+ add, ``relu_``)
 — the functional forms, so that no hook fires twice — and the bit patterns must be equal; otherwise the site is dropped with
@@ -37,6 +40,7 @@ _BN_FORWARD = nn.modules.batchnorm._BatchNorm.forward
 _PLANS: "weakref.WeakKeyDictionary[nn.Module, _Plan]" = weakref.WeakKeyDictionary()
 _ADDS = (operator.add, operator.iadd, torch.add)
 _RELUS = (F.relu, torch.relu, torch.relu_)
+_POOL_ARGS = ("kernel_size", "stride", "padding", "dilation", "ceil_mode", "return_indices")  # F.max_pool2d's, after the input
 
 
 def enabled() -> bool:
@@ -49,6 +53,29 @@ def _plain_bn(m) -> bool:
 
 def _plain_relu(m) -> bool:
     return isinstance(m, nn.ReLU) and type(m).forward is nn.ReLU.forward
+
+
+def _plain_pool(m) -> bool:
+    return isinstance(m, nn.MaxPool2d) and type(m).forward is nn.MaxPool2d.forward
+
+
+def _pair(v):
+    if isinstance(v, int) and not isinstance(v, bool):
+        return (v, v)
+    if isinstance(v, (tuple, list)) and len(v) == 2 and all(isinstance(e, int) and not isinstance(e, bool) for e in v):
+        return tuple(v)
+    return None
+
+
+def _pool_params(kernel_size, stride=None, padding=0, dilation=1, ceil_mode=False, return_indices=False):
+    """((kh, kw), (sh, sw), (ph, pw)) when the library's pooled epilogue computes this max_pool2d, else None."""
+    if ceil_mode or return_indices or _pair(dilation) != (1, 1):
+        return None
+    k, p = _pair(kernel_size), _pair(padding)
+    s = k if stride is None or stride == [] or stride == () else _pair(stride)
+    if k is None or s is None or p is None or not N.bn_pool_supported(k, s, p):
+        return None
+    return k, s, p
 
 
 def _hooked(m: nn.Module) -> bool:
@@ -65,12 +92,13 @@ def _streamable(t) -> bool:
 class _Site:
     """One BatchNorm2d of the model: which epilogues were proven bit-equal on it, or that it was dropped."""
 
-    __slots__ = ("bn", "verified", "dropped")
+    __slots__ = ("bn", "verified", "dropped", "no_pool")
 
     def __init__(self, bn: nn.BatchNorm2d):
         self.bn = bn
         self.verified: set = set()
         self.dropped = False
+        self.no_pool = False  # the pooled epilogue failed its proof here (the others may stand)
 
     def eligible(self, x) -> bool:
         bn = self.bn
@@ -105,6 +133,31 @@ class _Site:
             f"(relu={relu}, residual={other is not None}); this BatchNorm2d runs unfused from now on.", RuntimeWarning, stacklevel=3)
         return ref
 
+    def pool_eligible(self, x, params) -> bool:
+        (kh, kw), _, (ph, pw) = params
+        return (not self.no_pool and x.shape[3] <= N.BN_POOL_MAX_WIDTH and x.shape[2] + 2 * ph >= kh
+                and x.shape[3] + 2 * pw >= kw)
+
+    def run_pool(self, x, params):
+        bn = self.bn
+        k, s, p = params
+        out = N.batchnorm_infer_relu_maxpool(x, bn.running_mean, bn.running_var, bn.weight, bn.bias, bn.eps, k, s, p)
+        banded = x.shape[2] > N.BN_POOL_STAGE_BYTES // (4 * x.shape[3])  # the launch that splits a plane into bands of rows
+        key = ("pool", params, x.shape[3] % 4 == 0 and out.shape[3] % 4 == 0, banded)
+        if key in self.verified:
+            return out
+        ref = F.batch_norm(x, bn.running_mean, bn.running_var, bn.weight, bn.bias, False, 0.0, bn.eps)
+        ref = F.max_pool2d(torch.relu_(ref), k, s, p)
+        if out.shape == ref.shape and torch.equal(out.view(torch.int32), ref.view(torch.int32)):
+            self.verified.add(key)
+            return out
+        self.no_pool = True
+        warnings.warn(
+            f"the fused BatchNorm + ReLU + max-pool kernel did not reproduce PyTorch's result bit for bit on a {tuple(x.shape)} "
+            f"input (kernel_size={k}, stride={s}, padding={p}); this max-pool runs unfused from now on.", RuntimeWarning,
+            stacklevel=3)
+        return ref
+
 
 def _bn_forward(site: _Site):
     def forward(x):
@@ -133,6 +186,30 @@ class _Fused(nn.Module):
         if self.add is not None:
             out = self.add(out, other) if self.bn_first else self.add(other, out)
         return relu(out)
+
+
+class _FusedPool(nn.Module):
+    """``max_pool2d(relu(bn(x)))`` as one call.  ``pool`` is the user's ``nn.MaxPool2d`` or, for ``F.max_pool2d`` with literal
+    arguments, their dict.  A call that is not eligible runs ``inner`` (the fused ``relu(bn(x))``, which steps aside on its own
+    terms) and then the user's pool."""
+
+    def __init__(self, inner: _Fused, pool):
+        super().__init__()
+        self.__dict__.update(inner=inner, pool=pool)  # (not registered as children)
+
+    def forward(self, x):
+        inner, pool = self.inner, self.pool
+        site, relu = inner.site, inner.relu
+        if isinstance(pool, nn.Module):  # parameters are read now: the user may have changed them since the trace
+            params = _pool_params(*(getattr(pool, name) for name in _POOL_ARGS))
+            hooked = _hooked(pool)
+        else:
+            params, hooked = _pool_params(**pool), False
+        if (params is not None and not hooked and not _hooked(site.bn) and not (isinstance(relu, nn.Module) and _hooked(relu))
+                and site.eligible(x) and site.pool_eligible(x, params)):
+            return site.run_pool(x, params)
+        out = inner(x)
+        return pool(out) if isinstance(pool, nn.Module) else F.max_pool2d(out, **pool)
 
 
 def _trace(parent: nn.Module, sites: dict):
@@ -170,6 +247,22 @@ def _trace(parent: nn.Module, sites: dict):
             return F.relu
         return None
 
+    def pool_of(node, source):
+        """The user's pool module, or the keyword form of a literal ``F.max_pool2d`` call, when ``node`` pools ``source``."""
+        if not node.args or node.args[0] is not source:
+            return None
+        if node.op == "call_module" and _plain_pool(mods.get(node.target)) and len(node.args) == 1 and not node.kwargs:
+            return mods[node.target]
+        if node.op == "call_function" and node.target is F.max_pool2d and len(node.args) <= 1 + len(_POOL_ARGS):
+            given = dict(zip(_POOL_ARGS, node.args[1:]))
+            if set(given) & set(node.kwargs) or not set(node.kwargs) <= set(_POOL_ARGS):
+                return None
+            given.update(node.kwargs)
+            flat = [e for v in given.values() for e in (v if isinstance(v, (tuple, list)) else (v,))]
+            if "kernel_size" in given and not any(isinstance(e, fx.Node) for e in flat):
+                return given
+        return None
+
     n_fused = 0
     for node in list(graph.nodes):
         if node.op != "call_module" or mods.get(node.target) not in sites or node.kwargs or len(node.args) != 1:
@@ -180,6 +273,10 @@ def _trace(parent: nn.Module, sites: dict):
         last, fused, args = user, None, None
         if relu_of(user) is not None:
             fused, args = _Fused(site, relu_of(user)), (node.args[0],)
+            follower = next(iter(user.users)) if len(user.users) == 1 else None  # the pool must be the ReLU's only consumer
+            pool = pool_of(follower, user) if follower is not None else None
+            if pool is not None:
+                last, fused = follower, _FusedPool(fused, pool)
         elif (user.op == "call_function" and user.target in _ADDS and not user.kwargs and len(user.args) == 2
               and all(isinstance(a, fx.Node) for a in user.args) and user.args[0] is not user.args[1] and len(user.users) == 1):
             last = next(iter(user.users))
