@@ -19,6 +19,13 @@
  *    negative SL_E_* on failure; sl_last_error() returns a thread-local message.
  *  - No entry point allocates device memory; scratch is passed in by the caller.  The only object that
  *    outlives a call is the RCCL communicator of sl_comm_init_from_unique_id / sl_comm_destroy.
+ *  - Process state: what a call computes depends on its arguments alone, and a few process-wide settings choose HOW
+ *    (bit-identical variants, arithmetic mode, profiling).  The entry points that read or write them:
+ *    sl_set_reduce_policy (the default cache policy of the reduce calls that pass none: sl_reduce_conv, sl_reduce_tokens,
+ *    both *_multi, and a negative field of sl_reduce_*_p), sl_set_option / sl_get_option with the environment variable
+ *    SL_OPTIONS (read by the GEMM, K2 and K16 dispatchers), sl_set_gemm_mode (the cosine GEMMs) and sl_prof_enable /
+ *    sl_prof_reset / sl_prof_read (every profiled launch).  Setting one while another thread is inside a call that
+ *    reads it gives that call the old or the new value.
  *  - Strides are in ELEMENTS.
  */
 #ifndef SEMANTICLENS_AMD_H
@@ -86,13 +93,19 @@ int sl_device_count(void);
 int sl_reduce_conv(const void* d_act, int dtype, int64_t B, int64_t C, int64_t S, int64_t sb, int64_t sc,
                    int64_t ss, int agg, uint16_t* d_cand_bf16, float* d_out_f32, void* stream);
 
-/* Cache policy of K1's row streams, process-wide.  A COLD input streams best with the read-once (nt) policy; an input the
+/* Cache policy of the K1 / K2 streams.  A COLD input streams best with the read-once (nt) policy; an input the
  * previous kernel on the stream wrote microseconds ago is partly still in the 256 MiB Infinity Cache and reads faster
  * with the default policy.  Inputs smaller than nt_min_bytes are read with the default policy; of larger ones the last
- * tail_bytes likewise, the rest with nt.  Defaults (also: environment SL_NT_MIN_BYTES, SL_REDUCE_TAIL_MB in MiB):
- * 256 MiB / 240 MiB, i.e. "the input was just produced" — what a forward hook sees.  (0, 0) = everything nt, for
- * inputs known to be cold; negative values restore the defaults. */
+ * tail_bytes likewise, the rest with nt.  (0, 0) = everything nt, for inputs known to be cold.  Results do not depend on it.
+ *
+ * sl_reduce_conv_p / sl_reduce_tokens_p (below) take the policy as the call's last two arguments; a negative field takes
+ * the process default.  sl_set_reduce_policy sets that process default, for callers that do not pass a policy; negative
+ * values restore the built-in one: the environment (SL_NT_MIN_BYTES, SL_REDUCE_TAIL_MB in MiB, read once), else
+ * 256 MiB / 240 MiB, i.e. "the input was just produced" — what a forward hook sees. */
 int sl_set_reduce_policy(int64_t nt_min_bytes, int64_t tail_bytes);
+/* sl_reduce_conv with the cache policy of this call; sl_reduce_conv(...) is sl_reduce_conv_p(..., -1, -1) */
+int sl_reduce_conv_p(const void* d_act, int dtype, int64_t B, int64_t C, int64_t S, int64_t sb, int64_t sc, int64_t ss, int agg,
+                     uint16_t* d_cand_bf16, float* d_out_f32, void* stream, int64_t nt_min_bytes, int64_t tail_bytes);
 
 /* Relevance visualizer (relevance_based.py:112, abs_norm=True -> zennit-crp ChannelConcept.reference_sampling):
  * d_x (B,C) fp32 in place, x[b][:] /= (sum_c |x[b][c]| + eps). */
@@ -103,10 +116,14 @@ int sl_abs_norm_rows(float* d_x, int64_t B, int64_t C, float eps, void* stream);
  * `pos` is used by SL_TOK_TOKEN only (python-style negative index allowed). */
 int sl_reduce_tokens(const void* d_act, int dtype, int64_t B, int64_t T, int64_t F, int64_t sb, int64_t st,
                      int64_t sf, int agg, int64_t pos, uint16_t* d_cand_bf16, float* d_out_f32, void* stream);
+/* with the cache policy of this call (see sl_set_reduce_policy); sl_reduce_tokens(...) is sl_reduce_tokens_p(..., -1, -1) */
+int sl_reduce_tokens_p(const void* d_act, int dtype, int64_t B, int64_t T, int64_t F, int64_t sb, int64_t st, int64_t sf, int agg,
+                       int64_t pos, uint16_t* d_cand_bf16, float* d_out_f32, void* stream, int64_t nt_min_bytes, int64_t tail_bytes);
 
 /* The same reductions over L activations of ONE shape (the hooked outputs of L identical blocks, activation_caching.py:388-418
  * fires once per hooked layer and batch) in one launch where the component axis is contiguous, tensor by tensor otherwise.
- * h_d_acts: host array of L device pointers; d_cand_bf16: (L, B, C) contiguous. */
+ * h_d_acts: host array of L device pointers; d_cand_bf16: (L, B, C) contiguous.  Cache policy: the process default
+ * (sl_set_reduce_policy); nothing tunes these per call, so they have no _p form. */
 int sl_reduce_conv_multi(const void* const* h_d_acts, int L, int dtype, int64_t B, int64_t C, int64_t S, int64_t sb, int64_t sc,
                          int64_t ss, int agg, uint16_t* d_cand_bf16, void* stream);
 int sl_reduce_tokens_multi(const void* const* h_d_acts, int L, int dtype, int64_t B, int64_t T, int64_t F, int64_t sb, int64_t st,

@@ -199,9 +199,9 @@ class ActMax:
         if self._policy_tuner is None:
             self._policy_tuner = N.ReducePolicyTuner.for_site(site) if site is not None else N.ReducePolicyTuner()
         if kind == "conv":
-            self._policy_tuner.run(lambda: N.reduce_conv(x, code, cand, None), x.numel() * x.element_size(), B)
+            self._policy_tuner.run(lambda p: N.reduce_conv(x, code, cand, None, policy=p), x.numel() * x.element_size(), B)
         else:
-            self._policy_tuner.run(lambda: N.reduce_tokens(x, code, pos, cand, None), x.numel() * x.element_size(), B)
+            self._policy_tuner.run(lambda p: N.reduce_tokens(x, code, pos, cand, None, policy=p), x.numel() * x.element_size(), B)
         if self.tie_mode == "aten":
             if k3_queue is not None:
                 k3_queue(self, cand, id_base, B)

@@ -15,48 +15,30 @@
 //   reduce_row_half.hip  the same for fp16 / bf16: rowreduce_h, rowreduce_dma (the kernel itself: reduce_dma.hpp).
 //   reduce_col.hip       reduced axis strided, component axis contiguous (tokens (B,T,F), or channels_last conv): lanes along
 //                        F with 16-byte loads, the waves of a workgroup split T and combine through LDS.  colreduce2, colreduce.
-//   this file            generic (any strides, any dtype: one lane per output element), the dispatch, the cache-policy state,
+//   this file            generic (any strides, any dtype: one lane per output element), the dispatch, the cache policy's process default,
 //                        the C entry points, and abs_norm_rows.
 // reduce_common.hpp holds what the units share and declares what crosses them.
+#include <atomic>
 #include <cstdlib>
 
 #include "reduce_common.hpp"
 
 namespace sl {
 
-// ---- cache policy of the reduce streams (sl_set_reduce_policy; environment SL_NT_MIN_BYTES / SL_REDUCE_TAIL_MB) ----
-// A COLD input streams best with the nt (read-once) policy: 6.4 vs 5.9 TB/s on 411 MB.  Inside a model the input was
-// written by the previous kernel microseconds ago; what still sits (dirty) in the 256 MiB Infinity Cache reads faster
-// with the default policy and nt on it LOSES (in-bench average 5.0 TB/s all-nt vs 5.9 mixed).  The kernel cannot know
-// its producer, so the default assumes the common case — a forward hook on the layer that just ran: inputs below
-// `nt_min_bytes` (default 256 MiB) are read with the default policy; of larger ones the last `tail_bytes` (default
-// 240 MiB: what the cache still holds) likewise and the head with nt.  tail_bytes = 0 and nt_min_bytes = 0 = all nt,
-// the right setting for inputs known to be cold.  The kernels walk the tail FIRST — the most recently written bytes are
-// read while the cache still holds them (in-pipeline 411 MB: 6.07 -> 6.44 TB/s) — and inputs read entirely with the default
-// policy front to back.
-static int64_t g_nt_min_bytes = -1, g_tail_bytes = -1;
-static int64_t nt_min_bytes_() {
-  if (g_nt_min_bytes < 0) {
-    const char* e = getenv("SL_NT_MIN_BYTES");
-    g_nt_min_bytes = e ? (int64_t)atoll(e) : (int64_t)256 << 20;
-  }
-  return g_nt_min_bytes;
-}
-static int64_t tail_bytes_() {
-  if (g_tail_bytes < 0) {
-    const char* e = getenv("SL_REDUCE_TAIL_MB");
-    g_tail_bytes = (e ? (int64_t)atoll(e) : (int64_t)240) << 20;
-  }
-  return g_tail_bytes;
-}
+// ---- process default of the cache policy (reduce_policy.hpp), for calls that pass none: sl_set_reduce_policy, else the
+// environment (SL_NT_MIN_BYTES, SL_REDUCE_TAIL_MB in MiB), else 256 MiB / 240 MiB.  A stored -1 = not set by a caller
+static std::atomic<int64_t> g_default_nt_min{-1}, g_default_tail{-1};
 
-bool nt_policy_applies(int64_t bytes) { return bytes >= nt_min_bytes_(); }
-
-int64_t nt_head_units(int64_t bytes, int64_t unit_bytes, int64_t scale, int64_t tail_cap) {
-  if (!nt_policy_applies(bytes)) return 0;
-  const int64_t tail = tail_bytes_() < tail_cap ? tail_bytes_() : tail_cap;
-  if (tail <= 0) return INT64_MAX;
-  return bytes > tail ? (bytes - tail) / unit_bytes * scale : 0;
+// a negative field of a call's policy takes the process default
+static ReducePolicy resolve_policy(int64_t nt_min_bytes, int64_t tail_bytes) {
+  static const ReducePolicy env = [] {  // read once; initialisation of a local static is thread-safe
+    const char* n = getenv("SL_NT_MIN_BYTES");
+    const char* t = getenv("SL_REDUCE_TAIL_MB");
+    return ReducePolicy{n ? (int64_t)atoll(n) : (int64_t)256 << 20, (t ? (int64_t)atoll(t) : (int64_t)240) << 20};
+  }();
+  if (nt_min_bytes < 0) nt_min_bytes = g_default_nt_min.load(std::memory_order_relaxed);
+  if (tail_bytes < 0) tail_bytes = g_default_tail.load(std::memory_order_relaxed);
+  return ReducePolicy{nt_min_bytes < 0 ? env.nt_min_bytes : nt_min_bytes, tail_bytes < 0 ? env.tail_bytes : tail_bytes};
 }
 
 int bad_reduce_op(const char* who, int op) {
@@ -101,45 +83,47 @@ __global__ __launch_bounds__(256) void generic_reduce_kernel(const void* __restr
 }
 
 template <typename T, int OP>
-void launch_generic(ProfScope& prof, const void* x, int64_t B, int64_t C, int64_t S, int64_t sb, int64_t sc, int64_t ss, int64_t s0,
-                    int64_t s1, float denom, uint16_t* cand, float* outf, hipStream_t st) {
-  SL_LAUNCH(prof, (generic_reduce_kernel<T, OP>), dim3(grid_blocks((B * C + 255) / 256, 16)), dim3(256), 0, st, x, B, C, S, sb, sc, ss,
-            s0, s1, denom, cand, outf);
+void launch_generic(const ReduceCall& c, const void* x, int64_t B, int64_t C, int64_t S, int64_t sb, int64_t sc, int64_t ss, int64_t s0,
+                    int64_t s1) {
+  SL_LAUNCH(c.prof, (generic_reduce_kernel<T, OP>), dim3(grid_blocks((B * C + 255) / 256, 16)), dim3(256), 0, c.st, x, B, C, S, sb, sc,
+            ss, s0, s1, c.denom, c.cand, c.outf);
 }
 
-int dispatch_generic(int op, ProfScope& prof, const void* x, int dtype, int64_t B, int64_t C, int64_t S, int64_t sb, int64_t sc,
-                     int64_t ss, int64_t s0, int64_t s1, float denom, uint16_t* cand, float* outf, hipStream_t st) {
+int dispatch_generic(int op, const ReduceCall& c, const void* x, int dtype, int64_t B, int64_t C, int64_t S, int64_t sb, int64_t sc,
+                     int64_t ss, int64_t s0, int64_t s1) {
   if (dtype == SL_F32) {
-    SL_SWITCH_OP(op, launch_generic<float, OP>(prof, x, B, C, S, sb, sc, ss, s0, s1, denom, cand, outf, st); return 0);
+    SL_SWITCH_OP(op, launch_generic<float, OP>(c, x, B, C, S, sb, sc, ss, s0, s1); return 0);
   } else if (dtype == SL_F16) {
-    SL_SWITCH_OP(op, launch_generic<_Float16, OP>(prof, x, B, C, S, sb, sc, ss, s0, s1, denom, cand, outf, st); return 0);
+    SL_SWITCH_OP(op, launch_generic<_Float16, OP>(c, x, B, C, S, sb, sc, ss, s0, s1); return 0);
   } else {
-    SL_SWITCH_OP(op, launch_generic<uint16_t, OP>(prof, x, B, C, S, sb, sc, ss, s0, s1, denom, cand, outf, st); return 0);
+    SL_SWITCH_OP(op, launch_generic<uint16_t, OP>(c, x, B, C, S, sb, sc, ss, s0, s1); return 0);
   }
   return bad_reduce_op("dispatch_generic", op);
 }
 
+// what the sums over [s0, s1) are divided by.  x / 1 is exact: the same kernels give plain sums
+float reduce_denom(int64_t s0, int64_t s1, bool plain_sum) { return plain_sum ? 1.f : (float)(s1 - s0); }
+
 // (B, C, S) with strides -> (B, C): reduce over s in [s0, s1).  Picks the fastest legal path.
-int reduce_dispatch(int op, ProfScope& prof, const void* x, int dtype, int64_t B, int64_t C, int64_t S, int64_t sb, int64_t sc,
-                    int64_t ss, int64_t s0, int64_t s1, uint16_t* cand, float* outf, hipStream_t st, bool plain_sum = false) {
-  const float denom = plain_sum ? 1.f : (float)(s1 - s0);  // x / 1 is exact: the same kernels give sums
+int reduce_dispatch(int op, const ReduceCall& c, const void* x, int dtype, int64_t B, int64_t C, int64_t S, int64_t sb, int64_t sc,
+                    int64_t ss, int64_t s0, int64_t s1) {
   const bool aligned = ((uintptr_t)x & 15) == 0;
   const bool full = (s0 == 0 && s1 == S);
   int rc = 0;
   if (dtype == SL_F32 && aligned && full && ss == 1 && sc == S && sb == C * S && S < (1 << 28)) {
-    rc = dispatch_rowreduce(op, prof, (const float*)x, B * C, (int)S, denom, cand, outf, st);
+    rc = dispatch_rowreduce(op, c, (const float*)x, B * C, (int)S);
   } else if (dtype == SL_F32 && aligned && sc == 1 && (C % 4) == 0 && (ss % 4) == 0 && (sb % 4) == 0 &&
              S < (1 << 30)) {
-    rc = launch_colreduce(op, dtype, prof, x, B, (int)S, C, sb, ss, (int)s0, (int)s1, denom, cand, outf, st);
+    rc = launch_colreduce(op, dtype, c, x, B, (int)S, C, sb, ss, (int)s0, (int)s1);
   } else if (dtype != SL_F32 && aligned && full && ss == 1 && sc == S && sb == C * S && S > 0 && S < (1 << 27)) {
     // fp16 / bf16, NCHW-contiguous rows
-    rc = dispatch_rowreduce_h(op, dtype, prof, x, B * C, (int)S, denom, cand, outf, st);
+    rc = dispatch_rowreduce_h(op, dtype, c, x, B * C, (int)S);
   } else if (dtype != SL_F32 && ((uintptr_t)x & 7) == 0 && sc == 1 && (C % 4) == 0 && (ss % 4) == 0 && (sb % 4) == 0 &&
              S < (1 << 30)) {
     // fp16 / bf16, component axis contiguous (channels_last, tokens): 8-byte loads of four components
-    rc = launch_colreduce(op, dtype, prof, x, B, (int)S, C, sb, ss, (int)s0, (int)s1, denom, cand, outf, st);
+    rc = launch_colreduce(op, dtype, c, x, B, (int)S, C, sb, ss, (int)s0, (int)s1);
   } else {
-    rc = dispatch_generic(op, prof, x, dtype, B, C, S, sb, sc, ss, s0, s1, denom, cand, outf, st);
+    rc = dispatch_generic(op, c, x, dtype, B, C, S, sb, sc, ss, s0, s1);
   }
   if (rc) return rc;
   hipError_t e = hipGetLastError();
@@ -150,10 +134,12 @@ int reduce_dispatch(int op, ProfScope& prof, const void* x, int dtype, int64_t B
 int dtype_size(int dtype) { return dtype == SL_F32 ? 4 : 2; }
 
 // L same-shape (B, C, S) activations -> (L, B, C) candidates.  ONE launch when the component axis is contiguous (tokens,
-// channels_last: colreduce2 over a table of tensors), tensor by tensor otherwise — the same values either way.
+// channels_last: colreduce2 over a table of tensors), tensor by tensor otherwise — the same values either way.  Nothing tunes
+// these per call: the cache policy is the process default.
 int reduce_dispatch_multi(int op, const void* const* xs, int L, int dtype, int64_t B, int64_t C, int64_t S, int64_t sb, int64_t sc,
                           int64_t ss, int64_t s0, int64_t s1, uint16_t* cand, hipStream_t st, bool plain_sum = false) {
-  const float denom = plain_sum ? 1.f : (float)(s1 - s0);
+  const float denom = reduce_denom(s0, s1, plain_sum);
+  const ReducePolicy policy = resolve_policy(-1, -1);
   const double work = (double)B * C * (s1 - s0) * dtype_size(dtype);
   for (int l0 = 0; l0 < L; l0 += kMaxReduceSources) {
     const int n = L - l0 < kMaxReduceSources ? L - l0 : kMaxReduceSources;
@@ -161,7 +147,8 @@ int reduce_dispatch_multi(int op, const void* const* xs, int L, int dtype, int64
     bool done = false;
     if (n > 1 && sc == 1 && S < (1 << 30) && (ss % 4) == 0 && (sb % 4) == 0 && (C % 4) == 0) {
       ProfScope prof(SL_PROF_REDUCE, st, work * n);
-      const int rc = launch_colreduce2(op, dtype, prof, xs + l0, B, n * B, (int)S, C, sb, ss, (int)s0, (int)s1, denom, out, nullptr, st);
+      const int rc = launch_colreduce2(op, dtype, ReduceCall{prof, st, denom, out, nullptr, policy}, xs + l0, B, n * B, (int)S, C, sb, ss,
+                                       (int)s0, (int)s1);
       if (rc < 0) return rc;
       done = rc > 0;
       if (done) {
@@ -172,7 +159,8 @@ int reduce_dispatch_multi(int op, const void* const* xs, int L, int dtype, int64
     if (!done) {
       for (int i = 0; i < n; ++i) {
         ProfScope prof(SL_PROF_REDUCE, st, work);
-        const int rc = reduce_dispatch(op, prof, xs[l0 + i], dtype, B, C, S, sb, sc, ss, s0, s1, out + (int64_t)i * B * C, nullptr, st, plain_sum);
+        const int rc = reduce_dispatch(op, ReduceCall{prof, st, denom, out + (int64_t)i * B * C, nullptr, policy}, xs[l0 + i], dtype, B, C, S,
+                                       sb, sc, ss, s0, s1);
         if (rc) return rc;
       }
     }
@@ -221,8 +209,8 @@ __global__ __launch_bounds__(256) void abs_norm_rows_kernel(float* __restrict__ 
 using namespace sl;
 
 // ---- C entry points ------------------------------------------------------------------------------------------------------
-SL_API int sl_reduce_conv(const void* d_act, int dtype, int64_t B, int64_t C, int64_t S, int64_t sb, int64_t sc,
-                          int64_t ss, int agg, uint16_t* d_cand_bf16, float* d_out_f32, void* stream) {
+SL_API int sl_reduce_conv_p(const void* d_act, int dtype, int64_t B, int64_t C, int64_t S, int64_t sb, int64_t sc, int64_t ss, int agg,
+                            uint16_t* d_cand_bf16, float* d_out_f32, void* stream, int64_t nt_min_bytes, int64_t tail_bytes) {
   SL_REQUIRE(d_act || B * C * S == 0, "sl_reduce_conv: null activation");
   SL_REQUIRE(dtype >= SL_F32 && dtype <= SL_BF16, "sl_reduce_conv: bad dtype %d", dtype);
   SL_REQUIRE(B >= 0 && C >= 0 && S >= 0, "sl_reduce_conv: negative shape");
@@ -231,8 +219,13 @@ SL_API int sl_reduce_conv(const void* d_act, int dtype, int64_t B, int64_t C, in
   if (B * C == 0) return 0;
   hipStream_t st = (hipStream_t)stream;
   ProfScope prof(SL_PROF_REDUCE, st, (double)B * C * S * dtype_size(dtype));
-  return reduce_dispatch(agg == SL_CONV_MAX ? OP_MAX : OP_SUM, prof, d_act, dtype, B, C, S, sb, sc, ss, 0, S, d_cand_bf16, d_out_f32, st,
-                         agg == SL_CONV_SUM);
+  const ReduceCall c{prof, st, reduce_denom(0, S, agg == SL_CONV_SUM), d_cand_bf16, d_out_f32, resolve_policy(nt_min_bytes, tail_bytes)};
+  return reduce_dispatch(agg == SL_CONV_MAX ? OP_MAX : OP_SUM, c, d_act, dtype, B, C, S, sb, sc, ss, 0, S);
+}
+
+SL_API int sl_reduce_conv(const void* d_act, int dtype, int64_t B, int64_t C, int64_t S, int64_t sb, int64_t sc,
+                          int64_t ss, int agg, uint16_t* d_cand_bf16, float* d_out_f32, void* stream) {
+  return sl_reduce_conv_p(d_act, dtype, B, C, S, sb, sc, ss, agg, d_cand_bf16, d_out_f32, stream, -1, -1);
 }
 
 SL_API int sl_reduce_conv_multi(const void* const* h_d_acts, int L, int dtype, int64_t B, int64_t C, int64_t S, int64_t sb, int64_t sc,
@@ -247,9 +240,9 @@ SL_API int sl_reduce_conv_multi(const void* const* h_d_acts, int L, int dtype, i
                                (hipStream_t)stream, agg == SL_CONV_SUM);
 }
 
-SL_API int sl_reduce_tokens(const void* d_act, int dtype, int64_t B, int64_t T, int64_t F, int64_t sb, int64_t st_,
-                            int64_t sf, int agg, int64_t pos, uint16_t* d_cand_bf16, float* d_out_f32,
-                            void* stream) {
+SL_API int sl_reduce_tokens_p(const void* d_act, int dtype, int64_t B, int64_t T, int64_t F, int64_t sb, int64_t st_, int64_t sf, int agg,
+                              int64_t pos, uint16_t* d_cand_bf16, float* d_out_f32, void* stream, int64_t nt_min_bytes,
+                              int64_t tail_bytes) {
   SL_REQUIRE(d_act || B * T * F == 0, "sl_reduce_tokens: null activation");
   SL_REQUIRE(dtype >= SL_F32 && dtype <= SL_BF16, "sl_reduce_tokens: bad dtype %d", dtype);
   SL_REQUIRE(B >= 0 && T >= 0 && F >= 0, "sl_reduce_tokens: negative shape");
@@ -261,7 +254,14 @@ SL_API int sl_reduce_tokens(const void* d_act, int dtype, int64_t B, int64_t T, 
   int64_t t0, t1;
   if (const int rc = token_plan(agg, pos, T, &op, &t0, &t1)) return rc;
   ProfScope prof(SL_PROF_REDUCE, st, (double)B * (t1 - t0) * F * dtype_size(dtype));
-  return reduce_dispatch(op, prof, d_act, dtype, B, F, T, sb, sf, st_, t0, t1, d_cand_bf16, d_out_f32, st);
+  const ReduceCall c{prof, st, reduce_denom(t0, t1, false), d_cand_bf16, d_out_f32, resolve_policy(nt_min_bytes, tail_bytes)};
+  return reduce_dispatch(op, c, d_act, dtype, B, F, T, sb, sf, st_, t0, t1);
+}
+
+SL_API int sl_reduce_tokens(const void* d_act, int dtype, int64_t B, int64_t T, int64_t F, int64_t sb, int64_t st_,
+                            int64_t sf, int agg, int64_t pos, uint16_t* d_cand_bf16, float* d_out_f32,
+                            void* stream) {
+  return sl_reduce_tokens_p(d_act, dtype, B, T, F, sb, st_, sf, agg, pos, d_cand_bf16, d_out_f32, stream, -1, -1);
 }
 
 SL_API int sl_reduce_tokens_multi(const void* const* h_d_acts, int L, int dtype, int64_t B, int64_t T, int64_t F, int64_t sb, int64_t st_,
@@ -280,8 +280,8 @@ SL_API int sl_reduce_tokens_multi(const void* const* h_d_acts, int L, int dtype,
 
 SL_API int sl_set_reduce_policy(int64_t nt_min_bytes, int64_t tail_bytes) {
   // negative = back to the environment / built-in defaults
-  g_nt_min_bytes = nt_min_bytes < 0 ? -1 : nt_min_bytes;
-  g_tail_bytes = tail_bytes < 0 ? -1 : tail_bytes;
+  g_default_nt_min.store(nt_min_bytes < 0 ? -1 : nt_min_bytes, std::memory_order_relaxed);
+  g_default_tail.store(tail_bytes < 0 ? -1 : tail_bytes, std::memory_order_relaxed);
   return 0;
 }
 

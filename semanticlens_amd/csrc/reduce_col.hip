@@ -225,18 +225,17 @@ __global__ __launch_bounds__(64 * NW) void colreduce2_kernel(MultiSrc src, int64
 // per SIMD); with 8 the half-precision kernels need 140 registers and fall from 5.3 to 4.0 TB/s, fp32 gains nothing
 constexpr int kCol2Infl = 4;
 template <typename T, int OP, int NW, int LPR>
-void launch_colreduce2_as(ProfScope& prof, const MultiSrc& x, int64_t B, int T_, int64_t F, int64_t sb, int64_t st_, int t0, int t1,
-                          float denom, int64_t tail_from, uint16_t* cand, float* outf, hipStream_t st) {
+void launch_colreduce2_as(const ReduceCall& c, const MultiSrc& x, int64_t B, int T_, int64_t F, int64_t sb, int64_t st_, int t0, int t1,
+                          int64_t tail_from) {
   constexpr int CW = LPR * (16 / (int)sizeof(T));
   const unsigned blocks = grid_blocks(B * ((F + CW - 1) / CW), 8);
-  SL_LAUNCH(prof, (colreduce2_kernel<T, OP, NW, LPR, kCol2Infl>), dim3(blocks), dim3(64 * NW), 0, st, x, B, T_, F, sb, st_, t0,
-            t1, denom, tail_from, cand, outf);
+  SL_LAUNCH(c.prof, (colreduce2_kernel<T, OP, NW, LPR, kCol2Infl>), dim3(blocks), dim3(64 * NW), 0, c.st, x, B, T_, F, sb, st_, t0,
+            t1, c.denom, tail_from, c.cand, c.outf);
 }
 
 // `x`: a table of L = B / x.per tensors of x.per batches each (L = 1: one tensor); B counts the batches of all of them
 template <typename T, int OP>
-bool launch_colreduce2_t(ProfScope& prof, const MultiSrc& x, int64_t B, int T_, int64_t F, int64_t sb, int64_t st_, int t0, int t1,
-                       float denom, uint16_t* cand, float* outf, hipStream_t st) {
+bool launch_colreduce2_t(const ReduceCall& c, const MultiSrc& x, int64_t B, int T_, int64_t F, int64_t sb, int64_t st_, int t0, int t1) {
   const int forced_nw = (int)option(OPT_COLREDUCE_NW);  // sl_set_option("colreduce_nw", 4 / 8 / 16): tests walk every instance
   constexpr int EPP = 16 / (int)sizeof(T);
   const int64_t rows = t1 - t0;
@@ -258,7 +257,7 @@ bool launch_colreduce2_t(ProfScope& prof, const MultiSrc& x, int64_t B, int T_, 
   const int64_t per_b = (int64_t)T_ * F * (int64_t)sizeof(T);
   // cache policy in tasks = (b, chunk) pairs, b-major like the bytes.  Of a table of tensors only the LAST one was written a
   // moment ago: the default-policy tail never reaches into the others
-  const int64_t tail_from = nt_head_units(B * per_b, per_b, nchunk, L > 1 ? x.per * per_b : INT64_MAX);
+  const int64_t tail_from = nt_head_units(c.policy, B * per_b, per_b, nchunk, L > 1 ? x.per * per_b : INT64_MAX);
   // waves per task split the reduced axis; a wave instruction covers 64 / lpr rows, so short axes want few waves
   const int64_t inst_rows = rows * lpr / 64;  // wave instructions per task
   // 8 waves per task only below two tasks per CU.  tools/k2_lab.py (an elementwise producer, then K2) showed the fp32 kernel
@@ -274,7 +273,7 @@ bool launch_colreduce2_t(ProfScope& prof, const MultiSrc& x, int64_t B, int T_, 
   if (tasks_one * 2 < cus && inst_rows >= 128 && lpr == 64) nw = 16;
   else if (tasks_one < (sizeof(T) == 4 ? 2 : 1) * cus && inst_rows >= 64) nw = 8;
   if (forced_nw == 4 || forced_nw == 8 || (forced_nw == 16 && lpr == 64)) nw = forced_nw;
-#define SL_COL2(NW_, LPR_) launch_colreduce2_as<T, OP, NW_, LPR_>(prof, x, B, T_, F, sb, st_, t0, t1, denom, tail_from, cand, outf, st)
+#define SL_COL2(NW_, LPR_) launch_colreduce2_as<T, OP, NW_, LPR_>(c, x, B, T_, F, sb, st_, t0, t1, tail_from)
 #define SL_COL2_NW(LPR_)                 \
   do {                                   \
     if (nw == 16) SL_COL2(16, LPR_);     \
@@ -296,16 +295,15 @@ bool launch_colreduce2_t(ProfScope& prof, const MultiSrc& x, int64_t B, int T_, 
 }
 
 template <typename T, int OP>
-void launch_colreduce_t(ProfScope& prof, const T* x, int64_t B, int T_, int64_t F, int64_t sb, int64_t st_, int t0, int t1,
-                      float denom, uint16_t* cand, float* outf, hipStream_t st) {
+void launch_colreduce_t(const ReduceCall& c, const T* x, int64_t B, int T_, int64_t F, int64_t sb, int64_t st_, int t0, int t1) {
   MultiSrc one;
   one.ptr[0] = x;
   one.per = B;
-  if (launch_colreduce2_t<T, OP>(prof, one, B, T_, F, sb, st_, t0, t1, denom, cand, outf, st)) return;
+  if (launch_colreduce2_t<T, OP>(c, one, B, T_, F, sb, st_, t0, t1)) return;
   const int64_t nchunk = (F + 255) / 256, per_b = (int64_t)T_ * F * (int64_t)sizeof(T);
   const unsigned blocks = grid_blocks(B * nchunk, 8);
   // cache policy in tasks = (b, chunk) pairs, b-major like the bytes
-  const int64_t tail_from = nt_head_units(B * per_b, per_b, nchunk);
+  const int64_t tail_from = nt_head_units(c.policy, B * per_b, per_b, nchunk);
   // waves per task (they split the reduced axis): enough of them that a CU holds ~24 waves with 8 loads in flight each.
   // (B, 197, 768) at B = 256 is 768 tasks: 4-wave workgroups put 12 waves on a CU (5.4 TB/s cold), 8-wave ones 24.
   const int forced_nw = (int)option(OPT_COLREDUCE_NW);
@@ -320,14 +318,14 @@ void launch_colreduce_t(ProfScope& prof, const T* x, int64_t B, int T_, int64_t 
   else if (tasks < 2 * cus && rows >= 64) nw = 8;
   if (forced_nw == 4 || forced_nw == 8 || forced_nw == 16) nw = forced_nw;
   if (nw == 16)
-    SL_LAUNCH(prof, (colreduce_kernel<T, OP, 16>), dim3(blocks), dim3(1024), 0, st, x, B, T_, F, sb, st_, t0, t1, denom,
-              tail_from, cand, outf);
+    SL_LAUNCH(c.prof, (colreduce_kernel<T, OP, 16>), dim3(blocks), dim3(1024), 0, c.st, x, B, T_, F, sb, st_, t0, t1, c.denom,
+              tail_from, c.cand, c.outf);
   else if (nw == 8)
-    SL_LAUNCH(prof, (colreduce_kernel<T, OP, 8>), dim3(blocks), dim3(512), 0, st, x, B, T_, F, sb, st_, t0, t1, denom,
-              tail_from, cand, outf);
+    SL_LAUNCH(c.prof, (colreduce_kernel<T, OP, 8>), dim3(blocks), dim3(512), 0, c.st, x, B, T_, F, sb, st_, t0, t1, c.denom,
+              tail_from, c.cand, c.outf);
   else
-    SL_LAUNCH(prof, (colreduce_kernel<T, OP, 4>), dim3(blocks), dim3(256), 0, st, x, B, T_, F, sb, st_, t0, t1, denom,
-              tail_from, cand, outf);
+    SL_LAUNCH(c.prof, (colreduce_kernel<T, OP, 4>), dim3(blocks), dim3(256), 0, c.st, x, B, T_, F, sb, st_, t0, t1, c.denom,
+              tail_from, c.cand, c.outf);
 }
 
 // dtype -> element tag T inside the statement
@@ -340,18 +338,18 @@ void launch_colreduce_t(ProfScope& prof, const T* x, int64_t B, int T_, int64_t 
 
 }  // namespace
 
-int launch_colreduce2(int op, int dtype, ProfScope& prof, const void* const* srcs, int64_t per, int64_t B, int T_, int64_t F,
-                      int64_t sb, int64_t st_, int t0, int t1, float denom, uint16_t* cand, float* outf, hipStream_t st) {
+int launch_colreduce2(int op, int dtype, const ReduceCall& c, const void* const* srcs, int64_t per, int64_t B, int T_, int64_t F,
+                      int64_t sb, int64_t st_, int t0, int t1) {
   MultiSrc x;
   for (int64_t l = 0; l < B / per; ++l) x.ptr[l] = srcs[l];
   x.per = per;
-  SL_SWITCH_OP(op, SL_SWITCH_DTYPE(dtype, return (launch_colreduce2_t<T, OP>(prof, x, B, T_, F, sb, st_, t0, t1, denom, cand, outf, st) ? 1 : 0)));
+  SL_SWITCH_OP(op, SL_SWITCH_DTYPE(dtype, return (launch_colreduce2_t<T, OP>(c, x, B, T_, F, sb, st_, t0, t1) ? 1 : 0)));
   return bad_reduce_op("launch_colreduce2", op);
 }
 
-int launch_colreduce(int op, int dtype, ProfScope& prof, const void* x, int64_t B, int T_, int64_t F, int64_t sb, int64_t st_,
-                     int t0, int t1, float denom, uint16_t* cand, float* outf, hipStream_t st) {
-  SL_SWITCH_OP(op, SL_SWITCH_DTYPE(dtype, launch_colreduce_t<T, OP>(prof, (const T*)x, B, T_, F, sb, st_, t0, t1, denom, cand, outf, st);
+int launch_colreduce(int op, int dtype, const ReduceCall& c, const void* x, int64_t B, int T_, int64_t F, int64_t sb, int64_t st_,
+                     int t0, int t1) {
+  SL_SWITCH_OP(op, SL_SWITCH_DTYPE(dtype, launch_colreduce_t<T, OP>(c, (const T*)x, B, T_, F, sb, st_, t0, t1);
                                    return 0));
   return bad_reduce_op("launch_colreduce", op);
 }

@@ -7,6 +7,7 @@
 #include <type_traits>
 
 #include "common.hpp"
+#include "reduce_policy.hpp"
 
 namespace sl {
 namespace {
@@ -297,14 +298,15 @@ inline unsigned grid_blocks(int64_t want, int per_cu) {
 
 }  // namespace
 
-// ---- cache policy of the streams (state and rationale: reduce.hip) ----------------------------------------------------------
-// true: the input is large enough (>= nt_min_bytes) for the nt / default split
-bool nt_policy_applies(int64_t bytes);
-// How many leading walk units of an input of `bytes` bytes are read with nt; the rest — the last min(tail_bytes, tail_cap)
-// bytes, what the Infinity Cache may still hold — with the default policy.  `unit_bytes` is the byte size of the kernel's
-// unit, `scale` the walk units per such unit.  0 = all default (input below nt_min_bytes or not longer than the tail),
-// INT64_MAX = all nt (tail_bytes = 0).
-int64_t nt_head_units(int64_t bytes, int64_t unit_bytes, int64_t scale = 1, int64_t tail_cap = INT64_MAX);
+// ---- what every launch function receives -----------------------------------------------------------------------------------
+struct ReduceCall {
+  ProfScope& prof;
+  hipStream_t st;
+  float denom;          // sums are divided by it (1: plain sum); the max family ignores it
+  uint16_t* cand;       // (B, C) bf16 and / or
+  float* outf;          // (B, C) fp32 outputs
+  ReducePolicy policy;  // resolved cache policy (reduce_policy.hpp)
+};
 
 // ---- the units' dispatchers: `op` is an Op, `dtype` SL_F32 / SL_F16 / SL_BF16; 0 or a negative SL_E_* (message set) ---------
 // a U the site's derivation excludes turned up: never pick another kernel silently
@@ -312,17 +314,15 @@ int dma_unreachable(const char* site, int u, int64_t R, int S);
 // SL_SWITCH_OP fell through: `op` is no Op.  Every dispatcher ends with this instead of launching nothing
 int bad_reduce_op(const char* who, int op);
 // reduce_row.hip: R contiguous rows of S floats, x 16-byte aligned
-int dispatch_rowreduce(int op, ProfScope& prof, const float* x, int64_t R, int S, float denom, uint16_t* cand, float* outf,
-                       hipStream_t st);
+int dispatch_rowreduce(int op, const ReduceCall& c, const float* x, int64_t R, int S);
 // reduce_row_half.hip: the same for 2-byte elements (dtype SL_F16 / SL_BF16)
-int dispatch_rowreduce_h(int op, int dtype, ProfScope& prof, const void* x, int64_t R, int S, float denom, uint16_t* cand,
-                         float* outf, hipStream_t st);
+int dispatch_rowreduce_h(int op, int dtype, const ReduceCall& c, const void* x, int64_t R, int S);
 // reduce_col.hip: out[b][f] = op over t in [t0, t1) of x[b][t][f], f contiguous.  launch_colreduce2 takes a table of
 // B / per tensors of `per` batches each and returns 1 = launched, 0 = 16-byte pieces are not legal for the input (nothing
 // launched), negative = error
-int launch_colreduce2(int op, int dtype, ProfScope& prof, const void* const* srcs, int64_t per, int64_t B, int T, int64_t F,
-                      int64_t sb, int64_t st_, int t0, int t1, float denom, uint16_t* cand, float* outf, hipStream_t st);
-int launch_colreduce(int op, int dtype, ProfScope& prof, const void* x, int64_t B, int T, int64_t F, int64_t sb, int64_t st_,
-                     int t0, int t1, float denom, uint16_t* cand, float* outf, hipStream_t st);
+int launch_colreduce2(int op, int dtype, const ReduceCall& c, const void* const* srcs, int64_t per, int64_t B, int T, int64_t F,
+                      int64_t sb, int64_t st_, int t0, int t1);
+int launch_colreduce(int op, int dtype, const ReduceCall& c, const void* x, int64_t B, int T, int64_t F, int64_t sb, int64_t st_,
+                     int t0, int t1);
 
 }  // namespace sl

@@ -223,7 +223,7 @@ __global__ __launch_bounds__(256) void rowreduce_dma_kernel(const T* __restrict_
 }
 
 template <typename T, int G, int U, int OP, bool ALIGNED, bool MULTI = false, int NI = kDmaMaxBatch / 1024>
-void launch_rowreduce_dma(ProfScope& prof, const T* x, int64_t R, int S, float denom, uint16_t* cand, float* outf, hipStream_t st) {
+void launch_rowreduce_dma(const ReduceCall& c, const T* x, int64_t R, int S) {
   constexpr int RPT = kWave / G;
   constexpr int ES = (int)sizeof(T);
   const int64_t nbatch = (R / RPT + U - 1) / U;
@@ -232,14 +232,14 @@ void launch_rowreduce_dma(ProfScope& prof, const T* x, int64_t R, int S, float d
   int per_cu = kDmaLdsPerCu / lds;
   if (per_cu > 8) per_cu = 8;                             // 32 waves per CU
   const unsigned blocks = grid_blocks((nbatch + 3) / 4, per_cu);
-  const int64_t tail_from = nt_head_units(R * (int64_t)S * ES, (int64_t)RPT * S * ES);  // tasks from here on: default policy
+  const int64_t tail_from = nt_head_units(c.policy, R * (int64_t)S * ES, (int64_t)RPT * S * ES);  // tasks from here on: default policy
   if (lds > 64 * 1024) {  // dynamic LDS past 64 KiB has to be allowed per kernel
     static const hipError_t allowed = hipFuncSetAttribute((const void*)rowreduce_dma_kernel<T, G, U, OP, ALIGNED, MULTI, NI>,
                                                           hipFuncAttributeMaxDynamicSharedMemorySize, kDmaLdsPerCu);
     (void)allowed;
   }
-  SL_LAUNCH(prof, (rowreduce_dma_kernel<T, G, U, OP, ALIGNED, MULTI, NI>), dim3(blocks), dim3(256), (size_t)lds, st, x, R,
-            S, denom, slot, tail_from, cand, outf);
+  SL_LAUNCH(c.prof, (rowreduce_dma_kernel<T, G, U, OP, ALIGNED, MULTI, NI>), dim3(blocks), dim3(256), (size_t)lds, c.st, x, R,
+            S, c.denom, slot, tail_from, c.cand, c.outf);
 }
 
 // U values a call site can reach, as a mask of (1 << U); NI = 16 (one 4-16 KiB task per batch) is kDmaU16K
@@ -250,8 +250,7 @@ constexpr int kDmaUAll = kDmaU1 | kDmaU2 | kDmaU3 | kDmaU4;
 // whole pieces or rows do not group into tasks, or the input is small: launch-bound either way; the kernel indexes tasks with
 // 32 bits), 1: launched, negative: a U outside UMASK — the set the call site derived from its guards, the only ones instantiated.
 template <int G, int OP, bool ALIGNED, typename T, bool MULTI, int UMASK>
-int try_rowreduce_dma(const char* site, ProfScope& prof, const T* x, int64_t R, int S, float denom, uint16_t* cand, float* outf,
-                      hipStream_t st) {
+int try_rowreduce_dma(const char* site, const ReduceCall& c, const T* x, int64_t R, int S) {
   constexpr int RPT = kWave / G;
   const int64_t task_bytes = (int64_t)RPT * S * (int64_t)sizeof(T);
   if (task_bytes > (MULTI && sizeof(T) == 2 ? 16 * 1024 : kDmaMaxBatch) || (task_bytes & 15) != 0 || R % RPT != 0 ||
@@ -261,7 +260,7 @@ int try_rowreduce_dma(const char* site, ProfScope& prof, const T* x, int64_t R, 
 #define SL_DMA_U(BIT_, U_, NI_)                                                                            \
   do {                                                                                                     \
     if constexpr ((UMASK & (BIT_)) != 0) {                                                                 \
-      launch_rowreduce_dma<T, G, U_, OP, ALIGNED, MULTI, NI_>(prof, x, R, S, denom, cand, outf, st);       \
+      launch_rowreduce_dma<T, G, U_, OP, ALIGNED, MULTI, NI_>(c, x, R, S);                                 \
       return 1;                                                                                            \
     } else {                                                                                               \
       return dma_unreachable(site, NI_ == 16 ? 16 : U_, R, S);                                             \

@@ -253,30 +253,30 @@ __global__ __launch_bounds__(256) void rowreduce_fast_kernel(const float* __rest
 }
 
 template <int G, int U, int OP>
-void launch_rowreduce(ProfScope& prof, const float* x, int64_t R, int S, float denom, uint16_t* cand, float* outf, hipStream_t st) {
+void launch_rowreduce(const ReduceCall& c, const float* x, int64_t R, int S) {
   constexpr int RPT = kWave / G;
   const int64_t ntasks = (R + RPT - 1) / RPT;
   const int64_t nbatch = (ntasks + U - 1) / U;
   const unsigned blocks = grid_blocks((nbatch + 3) / 4, 8);
   if ((R * (int64_t)S) % 4 == 0)
-    SL_LAUNCH(prof, (rowreduce_kernel<G, U, OP, false>), dim3(blocks), dim3(256), 0, st, x, R, S, denom, cand, outf);
+    SL_LAUNCH(c.prof, (rowreduce_kernel<G, U, OP, false>), dim3(blocks), dim3(256), 0, c.st, x, R, S, c.denom, c.cand, c.outf);
   else
-    SL_LAUNCH(prof, (rowreduce_kernel<G, U, OP, true>), dim3(blocks), dim3(256), 0, st, x, R, S, denom, cand, outf);
+    SL_LAUNCH(c.prof, (rowreduce_kernel<G, U, OP, true>), dim3(blocks), dim3(256), 0, c.st, x, R, S, c.denom, c.cand, c.outf);
 }
 
 template <int G, int U, int OP, bool ALIGNED>
-void launch_rowreduce_fast(ProfScope& prof, const float* x, int64_t R, int S, float denom, uint16_t* cand, float* outf, hipStream_t st) {
+void launch_rowreduce_fast(const ReduceCall& c, const float* x, int64_t R, int S) {
   constexpr int RPT = kWave / G;
   const int64_t nbatch = (R / RPT + U - 1) / U;
   const unsigned blocks = grid_blocks((nbatch + 3) / 4, 8);
   const int64_t bytes = R * (int64_t)S * 4;
   // cache policy in batches; inputs below nt_min_bytes take the instance whose every load has the default policy
-  if (nt_policy_applies(bytes)) {
-    const int64_t tail_from = nt_head_units(bytes, (int64_t)U * RPT * S * 4);
-    SL_LAUNCH(prof, (rowreduce_fast_kernel<G, U, OP, ALIGNED, kLoadAux>), dim3(blocks), dim3(256), 0, st, x, R, S, denom, cand, outf,
+  if (nt_policy_applies(c.policy, bytes)) {
+    const int64_t tail_from = nt_head_units(c.policy, bytes, (int64_t)U * RPT * S * 4);
+    SL_LAUNCH(c.prof, (rowreduce_fast_kernel<G, U, OP, ALIGNED, kLoadAux>), dim3(blocks), dim3(256), 0, c.st, x, R, S, c.denom, c.cand, c.outf,
               tail_from);
   } else {
-    SL_LAUNCH(prof, (rowreduce_fast_kernel<G, U, OP, ALIGNED, 0>), dim3(blocks), dim3(256), 0, st, x, R, S, denom, cand, outf,
+    SL_LAUNCH(c.prof, (rowreduce_fast_kernel<G, U, OP, ALIGNED, 0>), dim3(blocks), dim3(256), 0, c.st, x, R, S, c.denom, c.cand, c.outf,
               (int64_t)INT64_MAX);
   }
 }
@@ -285,19 +285,18 @@ void launch_rowreduce_fast(ProfScope& prof, const float* x, int64_t R, int S, fl
 // 64 / G rows is 1024 * np / G bytes.  The size conditions of try_rowreduce_dma (>= 8 MiB, R < 2^31) do not depend on G: a
 // site reached because an earlier site failed on them fails on them too.
 template <int OP>
-int dispatch_rowreduce_t(ProfScope& prof, const float* x, int64_t R, int S, float denom, uint16_t* cand, float* outf, hipStream_t st) {
+int dispatch_rowreduce_t(const ReduceCall& c, const float* x, int64_t R, int S) {
   // pieces needed for a row window: up to (S + 6) / 4
   const int need = (S + 6) / 4;
 #define SL_TRY_DMA(G_, AL_, MULTI_, UMASK_)                                                                                     \
   do {                                                                                                                          \
-    const int t_ = try_rowreduce_dma<G_, OP, AL_, float, MULTI_, UMASK_>("fp32 G=" #G_ " aligned=" #AL_ " multi=" #MULTI_, prof, x, R, \
-                                                                          S, denom, cand, outf, st);                            \
+    const int t_ = try_rowreduce_dma<G_, OP, AL_, float, MULTI_, UMASK_>("fp32 G=" #G_ " aligned=" #AL_ " multi=" #MULTI_, c, x, R, S); \
     if (t_) return t_ < 0 ? t_ : 0;                                                                                             \
   } while (0)
 #define SL_ROWREDUCE(G_, U_, AL_, UMASK_)                                            \
   do {                                                                               \
     SL_TRY_DMA(G_, AL_, false, UMASK_);                                              \
-    launch_rowreduce_fast<G_, U_, OP, AL_>(prof, x, R, S, denom, cand, outf, st);    \
+    launch_rowreduce_fast<G_, U_, OP, AL_>(c, x, R, S);                              \
     return 0;                                                                        \
   } while (0)
   // fast path A: rows are whole 16-byte pieces
@@ -348,20 +347,19 @@ int dispatch_rowreduce_t(ProfScope& prof, const float* x, int64_t R, int S, floa
   // tools/native/unaligned_probe.hip) — 17 x 17 4.7 -> 4.4 TB/s, 27 x 27 5.8 -> 5.4, 111 x 111 4.95 -> 5.26.
   // Every rung is reachable (rows that do not group into tasks, small inputs): S = 0..12 take G = 4, longer unaligned rows
   // the rung of their window, S >= 2^20 the last one.
-  if (need <= 4) launch_rowreduce<4, 8, OP>(prof, x, R, S, denom, cand, outf, st);
-  else if (need <= 8) launch_rowreduce<8, 8, OP>(prof, x, R, S, denom, cand, outf, st);
-  else if (need <= 16) launch_rowreduce<16, 8, OP>(prof, x, R, S, denom, cand, outf, st);
-  else if (need <= 32) launch_rowreduce<32, 8, OP>(prof, x, R, S, denom, cand, outf, st);
-  else if (need <= 64) launch_rowreduce<64, 8, OP>(prof, x, R, S, denom, cand, outf, st);
-  else launch_rowreduce<64, 4, OP>(prof, x, R, S, denom, cand, outf, st);
+  if (need <= 4) launch_rowreduce<4, 8, OP>(c, x, R, S);
+  else if (need <= 8) launch_rowreduce<8, 8, OP>(c, x, R, S);
+  else if (need <= 16) launch_rowreduce<16, 8, OP>(c, x, R, S);
+  else if (need <= 32) launch_rowreduce<32, 8, OP>(c, x, R, S);
+  else if (need <= 64) launch_rowreduce<64, 8, OP>(c, x, R, S);
+  else launch_rowreduce<64, 4, OP>(c, x, R, S);
   return 0;
 }
 
 }  // namespace
 
-int dispatch_rowreduce(int op, ProfScope& prof, const float* x, int64_t R, int S, float denom, uint16_t* cand, float* outf,
-                       hipStream_t st) {
-  SL_SWITCH_OP(op, return dispatch_rowreduce_t<OP>(prof, x, R, S, denom, cand, outf, st));
+int dispatch_rowreduce(int op, const ReduceCall& c, const float* x, int64_t R, int S) {
+  SL_SWITCH_OP(op, return dispatch_rowreduce_t<OP>(c, x, R, S));
   return bad_reduce_op("dispatch_rowreduce", op);
 }
 

@@ -125,19 +125,19 @@ __global__ __launch_bounds__(256) void rowreduce_h_kernel(const T* __restrict__ 
 }
 
 template <typename T, int G, int U, int J, int OP, bool ALIGNED>
-void launch_rowreduce_h(ProfScope& prof, const T* x, int64_t R, int S, float denom, uint16_t* cand, float* outf, hipStream_t st) {
+void launch_rowreduce_h(const ReduceCall& c, const T* x, int64_t R, int S) {
   constexpr int RPW = kWave / G;
   const int64_t nsets = (R + RPW - 1) / RPW;
   const int64_t nbatch = (nsets + U - 1) / U;
   const unsigned blocks = grid_blocks((nbatch + 3) / 4, 8);
-  const int64_t tail_from = nt_head_units(R * (int64_t)S * 2, (int64_t)U * RPW * S * 2);  // in batches
-  SL_LAUNCH(prof, (rowreduce_h_kernel<T, G, U, J, OP, ALIGNED>), dim3(blocks), dim3(256), 0, st, x, R, S, denom, tail_from,
-            cand, outf);
+  const int64_t tail_from = nt_head_units(c.policy, R * (int64_t)S * 2, (int64_t)U * RPW * S * 2);  // in batches
+  SL_LAUNCH(c.prof, (rowreduce_h_kernel<T, G, U, J, OP, ALIGNED>), dim3(blocks), dim3(256), 0, c.st, x, R, S, c.denom, tail_from,
+            c.cand, c.outf);
 }
 
 // G = lanes per row: the smallest power of two that covers the pieces of a row's window (at most 64: longer rows loop)
 template <typename T, int OP>
-int dispatch_rowreduce_h_t(ProfScope& prof, const T* x, int64_t R, int S, float denom, uint16_t* cand, float* outf, hipStream_t st) {
+int dispatch_rowreduce_h_t(const ReduceCall& c, const T* x, int64_t R, int S) {
   const bool al = S % 8 == 0;
   const int np = al ? S / 8 : (S + 14) / 8;
   // LDS-DMA ring kernel first (rowreduce_dma_kernel<T>: the fp32 kernel's feed with 8-element pieces); it takes inputs of
@@ -146,8 +146,7 @@ int dispatch_rowreduce_h_t(ProfScope& prof, const T* x, int64_t R, int S, float 
   // try_rowreduce_dma do not depend on G, so a site reached because an earlier one failed on them fails on them too.
 #define SL_TRY_DMA(G_, AL_, MULTI_, UMASK_)                                                                                  \
   do {                                                                                                                       \
-    const int t_ = try_rowreduce_dma<G_, OP, AL_, T, MULTI_, UMASK_>("half G=" #G_ " aligned=" #AL_ " multi=" #MULTI_, prof, x, R, S, \
-                                                                      denom, cand, outf, st);                                \
+    const int t_ = try_rowreduce_dma<G_, OP, AL_, T, MULTI_, UMASK_>("half G=" #G_ " aligned=" #AL_ " multi=" #MULTI_, c, x, R, S); \
     if (t_) return t_ < 0 ? t_ : 0;                                                                                          \
   } while (0)
   if (al) {
@@ -176,8 +175,8 @@ int dispatch_rowreduce_h_t(ProfScope& prof, const T* x, int64_t R, int S, float 
   // every rung below is reachable, aligned or not (small inputs; np = 1 is S = 8, or S = 1 unaligned)
 #define SL_ROWH(G, U, J)                                                                          \
   do {                                                                                            \
-    if (al) launch_rowreduce_h<T, G, U, J, OP, true>(prof, x, R, S, denom, cand, outf, st);       \
-    else launch_rowreduce_h<T, G, U, J, OP, false>(prof, x, R, S, denom, cand, outf, st);         \
+    if (al) launch_rowreduce_h<T, G, U, J, OP, true>(c, x, R, S);                                \
+    else launch_rowreduce_h<T, G, U, J, OP, false>(c, x, R, S);                                  \
     return 0;                                                                                     \
   } while (0)
   if (np <= 1) SL_ROWH(1, 4, 1);
@@ -193,12 +192,11 @@ int dispatch_rowreduce_h_t(ProfScope& prof, const T* x, int64_t R, int S, float 
 
 }  // namespace
 
-int dispatch_rowreduce_h(int op, int dtype, ProfScope& prof, const void* x, int64_t R, int S, float denom, uint16_t* cand,
-                         float* outf, hipStream_t st) {
+int dispatch_rowreduce_h(int op, int dtype, const ReduceCall& c, const void* x, int64_t R, int S) {
   if (dtype == SL_F16) {
-    SL_SWITCH_OP(op, return (dispatch_rowreduce_h_t<_Float16, OP>(prof, (const _Float16*)x, R, S, denom, cand, outf, st)));
+    SL_SWITCH_OP(op, return (dispatch_rowreduce_h_t<_Float16, OP>(c, (const _Float16*)x, R, S)));
   } else {
-    SL_SWITCH_OP(op, return (dispatch_rowreduce_h_t<uint16_t, OP>(prof, (const uint16_t*)x, R, S, denom, cand, outf, st)));
+    SL_SWITCH_OP(op, return (dispatch_rowreduce_h_t<uint16_t, OP>(c, (const uint16_t*)x, R, S)));
   }
   return bad_reduce_op("dispatch_rowreduce_h", op);
 }

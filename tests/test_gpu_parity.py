@@ -500,6 +500,105 @@ def test_conv_reduce_dma_every_reachable_site(dt, shape, site):
             assert d.max() <= 1, site  # <= 1 bf16 ulp (an ulp of fp16 or bf16 is at most one of bf16)
 
 
+def _plant_special_values(x: torch.Tensor) -> torch.Tensor:
+    """NaN at a row's first and at a row's last element, +inf, -inf and a row of -0.0, wherever they fall in `x`."""
+    flat = x.view(x.shape[0], -1)
+    flat[0, 0] = float("nan")
+    flat[-1, -1] = float("nan")
+    flat[x.shape[0] // 2, 7] = float("inf")
+    flat[x.shape[0] // 2, 8] = float("-inf")
+    if x.ndim == 4:
+        x[-1, 1].fill_(-0.0)
+    else:
+        x[-1, :, 1].fill_(-0.0)
+    return x
+
+
+@pytest.mark.gpu
+def test_reduce_per_call_policy_changes_no_bit():
+    """The cache policy passed with a call (`reduce_conv` / `reduce_tokens` `policy=`, `sl_reduce_*_p`) selects a load hint and
+    the order in which tasks are walked, never a value: every output equals, bit for bit, the same call with `policy=None`, which the
+    tests above pin to the oracle.  One input per host site that consults the policy, each the smallest that reaches the site, under
+    thresholds low enough that the nt / default split falls INSIDE these inputs; then the same through the process default
+    (`set_reduce_policy`) and the four entry points that take no policy, the table path of `reduce_multi` with its `tail_cap`
+    included."""
+    policies = [(0, 0), (1 << 20, 1 << 19), (1 << 20, 1 << 40), (1 << 40, 0), (None, 0)]
+    f32, f16, bf16 = torch.float32, torch.float16, torch.bfloat16
+    conv = [((4, 96, 56, 56), f32),      # rowreduce_fast: rows longer than a DMA batch
+            ((32, 1024, 8, 8), f32), ((4, 10700, 7, 7), f32),  # rowreduce_dma fp32, aligned and unaligned (8 MiB: the path's minimum)
+            ((4, 96, 56, 56), f16), ((4, 96, 56, 56), bf16),   # rowreduce_h
+            ((32, 1024, 8, 16), f16)]    # rowreduce_dma, 2-byte elements
+    tokens = [((16, 197, 768), f32),     # colreduce2
+              ((64, 197, 260), f16)]     # colreduce: F % 8 != 0, no 16-byte pieces
+    cases = [("conv", s, dt, code) for s, dt in conv for code in (N.SL_CONV_MAX, N.SL_CONV_MEAN)]
+    cases += [("tokens", s, dt, code) for s, dt in tokens for code in (N.SL_TOK_MEAN, N.SL_TOK_MAX)]
+    inputs = {}
+
+    def reduce(kind, xd, code, policy):
+        n_out = (xd.shape[0], xd.shape[1] if kind == "conv" else xd.shape[2])
+        cand = torch.empty(n_out, dtype=torch.bfloat16, device=DEV)
+        out = torch.empty(n_out, dtype=torch.float32, device=DEV)
+        if kind == "conv":
+            N.reduce_conv(xd, code, cand, out, policy=policy)
+        else:
+            N.reduce_tokens(xd, code, 0, cand, out, policy=policy)
+        return bits(cand), out.cpu().numpy().view(np.uint32)
+
+    def raw(kind, xd, code):  # the entry points without a policy argument, as INTEGRATION.md calls them
+        n_out = (xd.shape[0], xd.shape[1] if kind == "conv" else xd.shape[2])
+        cand = torch.empty(n_out, dtype=torch.bfloat16, device=DEV)
+        out = torch.empty(n_out, dtype=torch.float32, device=DEV)
+        with N._on(xd.device):
+            if kind == "conv":
+                B, C, H, W = xd.shape
+                flat, sb, sc, ss = N._flatten_spatial(xd)
+                rc = N.lib().sl_reduce_conv(N._ptr(flat), N._dtype_code(flat), B, C, H * W, sb, sc, ss, code, N._ptr(cand), N._ptr(out),
+                                            N._stream(flat))
+            else:
+                B, T, F = xd.shape
+                rc = N.lib().sl_reduce_tokens(N._ptr(xd), N._dtype_code(xd), B, T, F, *xd.stride(), code, 0, N._ptr(cand), N._ptr(out),
+                                              N._stream(xd))
+        assert rc == 0, N.lib().sl_last_error()
+        return bits(cand), out.cpu().numpy().view(np.uint32)
+
+    def multi(kind, xs, code):
+        cand = torch.empty((len(xs), xs[0].shape[0], xs[0].shape[1] if kind == "conv" else xs[0].shape[2]), dtype=torch.bfloat16, device=DEV)
+        N.reduce_multi(kind, xs, code, 0, cand)
+        return bits(cand)
+
+    want = {}
+    for case in cases:
+        kind, shape, dt, code = case
+        if (shape, dt) not in inputs:
+            g = torch.Generator().manual_seed(sum(shape))
+            inputs[shape, dt] = _plant_special_values((torch.randn(*shape, generator=g) + 2.0).to(dt)).to(DEV)
+        xd = inputs[shape, dt]
+        assert xd.numel() * xd.element_size() > 1 << 20  # the (1 MiB, 512 KiB) split falls inside the input
+        want[case] = reduce(kind, xd, code, None)
+        assert np.isnan(want[case][1].view(np.float32)).any()  # the planted values reached the output
+        for policy in policies:
+            got = reduce(kind, xd, code, policy)
+            assert np.array_equal(got[0], want[case][0]) and np.array_equal(got[1], want[case][1]), (case, policy)
+    # the table path: three same-shape token tensors in one launch, against the three single reductions
+    g = torch.Generator().manual_seed(5)
+    table = [_plant_special_values(torch.randn(4, 197, 768, generator=g) + 2.0).to(DEV) for _ in range(3)]
+    table_want = {code: np.stack([reduce("tokens", x, code, None)[0] for x in table]) for code in (N.SL_TOK_MEAN, N.SL_TOK_MAX)}
+    for code, w in table_want.items():
+        assert np.array_equal(multi("tokens", table, code), w), code
+    N.set_reduce_policy(1 << 20, 1 << 19)
+    try:
+        for case in cases:
+            kind, shape, dt, code = case
+            xd = inputs[shape, dt]
+            for got in (raw(kind, xd, code), reduce(kind, xd, code, None)):
+                assert np.array_equal(got[0], want[case][0]) and np.array_equal(got[1], want[case][1]), case
+            assert np.array_equal(multi(kind, [xd], code)[0], want[case][0]), case  # sl_reduce_*_multi, L = 1
+        for code, w in table_want.items():
+            assert np.array_equal(multi("tokens", table, code), w), code
+    finally:
+        N.set_reduce_policy(None, None)
+
+
 @pytest.mark.parametrize("dt", [torch.float16, torch.bfloat16])
 def test_half_precision_full_size_equals_torch(dt):
     """ResNet-50 layer shapes at the bench batch size: the kernels' max equals torch.amax bit for bit in both layouts."""

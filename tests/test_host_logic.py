@@ -3,6 +3,7 @@
 import re
 import subprocess
 import sys
+import threading
 from pathlib import Path
 from unittest import mock
 
@@ -47,6 +48,7 @@ def test_argument_errors_are_reported_without_a_device():
     assert lib.sl_similarity(None, 3, 4, None, 5, 6, None, None, 0, None) == -1
     assert lib.sl_last_error() == b"x and y must have the same shape"  # the reference's ValueError text
     assert lib.sl_reduce_conv(None, 7, 1, 1, 1, 1, 1, 1, 0, None, None, None) == -1
+    assert lib.sl_reduce_conv_p(None, 7, 1, 1, 1, 1, 1, 1, 0, None, None, None, -1, -1) == -1
     # the communicator entry points validate before they touch RCCL or a device
     assert lib.sl_comm_allgather(None, None, None, 16, None) == -1 and lib.sl_last_error() == b"sl_comm_allgather: null communicator"
     assert lib.sl_comm_allreduce(None, None, 4, 0, 0, None) == -1
@@ -746,60 +748,133 @@ def test_text_chunks_are_tokenised_one_ahead_in_the_same_order(monkeypatch):
     assert len(_encode_texts(FM(), texts, batch_size=None)) == 23  # one chunk: no thread
 
 
+class _FakeEvent:
+    """torch.cuda.Event for the tuner tests: records the calling thread's fake clock (`_fake_clock.now`), always complete."""
+
+    def __init__(self, enable_timing=True):
+        self.t = None
+
+    def record(self):
+        self.t = _fake_clock.now
+
+    def query(self):
+        return True
+
+    def elapsed_time(self, other):
+        return other.t - self.t
+
+
+_fake_clock = threading.local()
+
+
+def _tuner_launch(costs, seen):
+    """A launch for `ReducePolicyTuner.run`: records the policy it is GIVEN and costs what that policy says (None = the default)."""
+    cost = dict(zip(N.ReducePolicyTuner.CANDIDATES, costs))
+
+    def launch(policy):
+        seen.append(policy)
+        _fake_clock.now += cost[policy if policy is not None else (None, None)]
+
+    return launch
+
+
 def test_reduce_policy_tuner_measures_every_candidate_and_keeps_the_default_unless_clearly_slower(monkeypatch):
     """`N.ReducePolicyTuner`: one untimed + three timed launches per candidate, decision from the medians, the library default unless the
-    other policy is > 2 % faster; off for small inputs and once the caller chose a policy."""
-    applied = []
+    other policy is > 2 % faster; off for small inputs and once the caller chose a policy.  The policy reaches the launch as its
+    argument: the tuner never writes process state."""
     monkeypatch.delenv("SL_NT_MIN_BYTES", raising=False), monkeypatch.delenv("SL_REDUCE_TAIL_MB", raising=False)
     monkeypatch.setattr(N, "_policy_explicit", False)
-    clock = {"now": 0.0, "cost": {}}
+    monkeypatch.setattr(torch.cuda, "Event", _FakeEvent)
 
-    class Ev:
-        def __init__(self, enable_timing=True):
-            self.t = None
+    def no_process_state(*a, **kw):
+        raise AssertionError("the tuner wrote the process-wide reduce policy")
 
-        def record(self):
-            self.t = clock["now"]
-
-        def query(self):
-            return True
-
-        def elapsed_time(self, other):
-            return other.t - self.t
-
-    monkeypatch.setattr(torch.cuda, "Event", Ev)
-
-    # a launch costs what the policy in force says
-    current = [(None, None)]
-    monkeypatch.setattr(N, "_set_reduce_policy_raw", lambda a, b: (applied.append((a, b)), current.__setitem__(0, (a, b))))
+    monkeypatch.setattr(N, "set_reduce_policy", no_process_state)
+    monkeypatch.setattr(N.lib(), "sl_set_reduce_policy", no_process_state)
+    _fake_clock.now = 0.0
     cands = N.ReducePolicyTuner.CANDIDATES
     assert cands[0] == (None, None) and len(cands) == 3
     n_trials = 4 * len(cands)  # one untimed + three timed launches per candidate
 
     def go(tuner, costs, n=n_trials + 4, nbytes=200 << 20):
-        clock["cost"] = dict(zip(cands, costs))
-        for _ in range(n):
-            tuner.run(lambda: clock.__setitem__("now", clock["now"] + clock["cost"][current[0]]), nbytes, 256)
+        seen = []
+        launch = _tuner_launch(costs, seen)
+        for i in range(n):
+            tuner.run(launch, nbytes, 256)
+            if nbytes >= N.ReducePolicyTuner.MIN_BYTES and tuner.enabled():
+                assert (tuner.choice is None) == (i + 1 < n_trials)  # decided by exactly the last trial launch
+        return seen
 
     t = N.ReducePolicyTuner()
-    go(t, (1.0, 0.9, 0.95))
-    assert t.choice == 1 and applied.count(cands[1]) >= 4 + 4  # trials, then every launch under the chosen policy
-    assert applied[-1] == (None, None)  # always restored
+    seen = go(t, (1.0, 0.9, 0.95))
+    assert seen[:n_trials] == [cands[i % 3] for i in range(n_trials)]  # the candidates in turn, four launches each
+    assert t.choice == 1 and seen.count(cands[1]) >= 4 + 4  # trials, then every launch under the chosen policy
+    assert seen[n_trials:] == [cands[1]] * 4
     t = N.ReducePolicyTuner()
-    go(t, (1.0, 0.95, 0.9))
-    assert t.choice == 2  # the 128 MiB tail (round 5: outputs of three-stream residual adds)
+    seen = go(t, (1.0, 0.95, 0.9))
+    assert t.choice == 2 and seen[n_trials:] == [cands[2]] * 4  # the 128 MiB tail (round 5: outputs of three-stream residual adds)
     t = N.ReducePolicyTuner()
-    go(t, (1.0, 0.99, 0.985))
-    assert t.choice == 0  # within 2 %: the default stays
+    seen = go(t, (1.0, 0.99, 0.985))
+    assert t.choice == 0 and seen[n_trials:] == [None] * 4  # within 2 %: the default stays
     t = N.ReducePolicyTuner()
-    before = len(applied)
-    go(t, (1.0, 0.5, 0.5), nbytes=50 << 20)
-    assert t.choice is None and len(applied) == before  # below 96 MiB: never touched
+    seen = go(t, (1.0, 0.5, 0.5), nbytes=50 << 20)
+    assert t.choice is None and t._calls == 0 and seen == [None] * (n_trials + 4)  # below 96 MiB: never touched
     monkeypatch.setattr(N, "_policy_explicit", True)
     t = N.ReducePolicyTuner()
-    go(t, (1.0, 0.5, 0.5))
-    assert t.choice is None and len(applied) == before  # the caller's explicit policy wins
+    seen = go(t, (1.0, 0.5, 0.5))
+    assert t.choice is None and t._calls == 0 and seen == [None] * (n_trials + 4)  # the caller's explicit policy wins
     assert N.ReducePolicyTuner.for_site(("m", "layer")) is N.ReducePolicyTuner.for_site(("m", "layer"))
+
+
+def test_reduce_policy_tuners_on_two_threads_do_not_see_each_others_candidates(monkeypatch):
+    """Two collectors on two threads (prefetch threads, a second stream): their launches interleave pairwise (a barrier inside the
+    launch), and each launch still receives the candidate its OWN tuner's call count dictates, then its own choice."""
+    monkeypatch.delenv("SL_NT_MIN_BYTES", raising=False), monkeypatch.delenv("SL_REDUCE_TAIL_MB", raising=False)
+    monkeypatch.setattr(N, "_policy_explicit", False)
+    monkeypatch.setattr(torch.cuda, "Event", _FakeEvent)
+    cands = N.ReducePolicyTuner.CANDIDATES
+    n_trials, n = 4 * len(cands), 4 * len(cands) + 6
+    barrier = threading.Barrier(2, timeout=30)
+    tuners = [N.ReducePolicyTuner(), N.ReducePolicyTuner()]
+    costs = [(1.0, 0.9, 0.95), (1.0, 0.95, 0.9)]  # opposite tables
+    seen, errors = [[], []], []
+
+    def work(k):
+        try:
+            _fake_clock.now = 0.0
+            inner = _tuner_launch(costs[k], seen[k])
+
+            def launch(policy):
+                barrier.wait()  # both threads are inside a launch at the same time
+                inner(policy)
+                barrier.wait()
+
+            for _ in range(n):
+                tuners[k].run(launch, 200 << 20, 256)
+        except BaseException as e:  # noqa: BLE001 - reported by the main thread
+            errors.append(e)
+            barrier.abort()
+
+    threads = [threading.Thread(target=work, args=(k,)) for k in range(2)]
+    for th in threads:
+        th.start()
+    for th in threads:
+        th.join()
+    assert not errors, errors
+    assert [t.choice for t in tuners] == [1, 2]
+    for k in range(2):
+        assert seen[k] == [cands[i % 3] for i in range(n_trials)] + [cands[tuners[k].choice]] * (n - n_trials)
+
+
+def test_reduce_policy_header_on_the_host(tmp_path):
+    """csrc/reduce_policy.hpp compiled for the host: `nt_head_units` / `nt_policy_applies` of a resolved policy
+    (tests/native/reduce_policy_check.cpp holds the table)."""
+    exe = tmp_path / "reduce_policy_check"
+    subprocess.run(["g++", "-O2", "-std=c++17", "-Wall", "-Wextra", "-o", str(exe),
+                    str(ROOT / "tests" / "native" / "reduce_policy_check.cpp")], check=True)
+    res = subprocess.run([str(exe)], capture_output=True, text=True)
+    assert res.returncode == 0, res.stdout + res.stderr
+    assert "failures=0" in res.stdout
 
 
 # ---- the aten tie order's host self-test (VERDICT r05 #12): restatement vs the installed torch.topk, no device -----------------------

@@ -1,7 +1,7 @@
 // K2 through wave-private LDS-DMA rings — the variant VERDICT r03 #5 asked for, built and measured in round 4
 // (profiles/r04_k2_lab.txt): 5.6-6.1 TB/s cold on (256, 197, 768) fp32 against 6.2-6.3 for colreduce2's register ping-pong,
-// and 2.0-4.5 TB/s on half-precision inputs (its rings cap a CU at 16 waves).  Kept out of the shipped library; included by
-// semanticlens_amd/csrc/reduce.hip only under -DSL_K2_DMA_LAB (SL_COLREDUCE_IMPL=dma then selects it).  Known defect: the
+// and 2.0-4.5 TB/s on half-precision inputs (its rings cap a CU at 16 waves).  Kept out of the shipped library: a record that
+// compiles inside namespace sl after semanticlens_amd/csrc/reduce_common.hpp, <cstdlib> and <cstring> (SL_COLREDUCE_IMPL=dma selects it).  Known defect: the
 // (256, 257, 1024) bf16 mean differed from torch at depth 2 / 8 waves in the lab run — one more reason it is not shipped.
 #pragma once
 
@@ -130,8 +130,8 @@ __global__ __launch_bounds__(64 * NW) void colreduce_dma_kernel(const E* __restr
 // colreduce through the LDS-DMA rings when the layout allows and the input is large enough to be bandwidth-bound.
 // SL_COLREDUCE_IMPL = vgpr | dma (default: dma where legal), SL_COLREDUCE_DEPTH = 2 | 3 | 4, SL_COLREDUCE_NW = 4 | 8.
 template <typename T, int OP, int NW, int DEPTH>
-void launch_colreduce_dma_as(ProfScope& prof, const T* x, int64_t B, int T_, int64_t F, int64_t sb, int64_t st_, int t0, int t1,
-                             float denom, int64_t tail_from, uint16_t* cand, float* outf, hipStream_t st) {
+void launch_colreduce_dma_as(const ReduceCall& c, const T* x, int64_t B, int T_, int64_t F, int64_t sb, int64_t st_, int t0, int t1,
+                             int64_t tail_from) {
   constexpr int CW = 64 * (16 / (int)sizeof(T));
   const int lds = NW * DEPTH * kColRows * 1024 + 1024;
   auto kernel = colreduce_dma_kernel<T, OP, NW, DEPTH>;
@@ -143,12 +143,12 @@ void launch_colreduce_dma_as(ProfScope& prof, const T* x, int64_t B, int T_, int
   int64_t blocks = B * ((F + CW - 1) / CW);
   const int64_t cap = (int64_t)num_cus() * 8;
   if (blocks > cap) blocks = cap;
-  SL_LAUNCH(prof, kernel, dim3((unsigned)blocks), dim3(64 * NW), lds, st, x, B, T_, F, sb, st_, t0, t1, denom, tail_from, cand, outf);
+  SL_LAUNCH(c.prof, kernel, dim3((unsigned)blocks), dim3(64 * NW), lds, c.st, x, B, T_, F, sb, st_, t0, t1, c.denom, tail_from, c.cand,
+            c.outf);
 }
 
 template <typename T, int OP>
-bool launch_colreduce_dma(ProfScope& prof, const T* x, int64_t B, int T_, int64_t F, int64_t sb, int64_t st_, int t0, int t1,
-                          float denom, uint16_t* cand, float* outf, hipStream_t st) {
+bool launch_colreduce_dma(const ReduceCall& c, const T* x, int64_t B, int T_, int64_t F, int64_t sb, int64_t st_, int t0, int t1) {
   static const int impl = [] {  // only on request: the lab variant (tools/k2_lab.py)
     const char* e = getenv("SL_COLREDUCE_IMPL");
     return e && strcmp(e, "dma") == 0 ? 1 : 0;
@@ -170,16 +170,14 @@ bool launch_colreduce_dma(ProfScope& prof, const T* x, int64_t B, int T_, int64_
     return false;
   const int64_t nchunk = (F + CW - 1) / CW, tasks = B * nchunk, cus = num_cus();
   if (tasks * 2 < cus) return false;  // few long tasks: the 16-wave VGPR kernel
-  // cache policy (top of this file), in tasks = (b, chunk) pairs, b-major like the bytes
-  const int64_t nt_min_bytes = nt_min_bytes_(), tail_bytes = tail_bytes_();
-  const int64_t per_b = (int64_t)T_ * F * (int64_t)sizeof(T), all = B * per_b;
-  int64_t tail_from = 0;
-  if (all >= nt_min_bytes) tail_from = tail_bytes > 0 ? (all > tail_bytes ? (all - tail_bytes) / per_b * nchunk : 0) : INT64_MAX;
+  // cache policy (reduce_policy.hpp), in tasks = (b, chunk) pairs, b-major like the bytes
+  const int64_t per_b = (int64_t)T_ * F * (int64_t)sizeof(T);
+  const int64_t tail_from = nt_head_units(c.policy, B * per_b, per_b, nchunk);
   int nw = (tasks < 2 * cus && rows >= 64) ? 8 : 4;
   if (forced_nw == 4 || forced_nw == 8) nw = forced_nw;
   int depth = kColDepthDefault;
   if (forced_depth >= 2 && forced_depth <= 4) depth = forced_depth;
-#define SL_COLDMA(NW_, D_) launch_colreduce_dma_as<T, OP, NW_, D_>(prof, x, B, T_, F, sb, st_, t0, t1, denom, tail_from, cand, outf, st)
+#define SL_COLDMA(NW_, D_) launch_colreduce_dma_as<T, OP, NW_, D_>(c, x, B, T_, F, sb, st_, t0, t1, tail_from)
   if (nw == 8) {
     if (depth == 2) SL_COLDMA(8, 2);
     else if (depth == 3) SL_COLDMA(8, 3);
