@@ -449,6 +449,14 @@ int sl_batchnorm_infer(const float* d_x, int64_t B, int64_t C, int64_t HW, const
 int sl_batchnorm_infer_add_relu(const float* d_x, const float* d_residual, int64_t B, int64_t C, int64_t HW,
                                 const float* d_mean, const float* d_var, const float* d_scale, const float* d_bias,
                                 double eps, float* d_y, void* stream);
+/* K19: clamp_min(y_a + y_b, 0), y_a and y_b the BatchNorm values of two tensors of one shape under their own
+ * constants and eps, each rounded to fp32 before the add; y_a is the add's left operand.  The tail of a residual block whose
+ * shortcut ends in a BatchNorm.  C <= 2048 (two constant tables); anything else as above.  With profiling on, a call leaves two
+ * records in SL_PROF_BATCHNORM, the kernel's and an empty one: the slot counts BatchNorm2d evaluations. */
+int sl_batchnorm_infer_add_bn_relu(const float* d_xa, const float* d_mean_a, const float* d_var_a, const float* d_scale_a,
+                                   const float* d_bias_a, double eps_a, const float* d_xb, const float* d_mean_b,
+                                   const float* d_var_b, const float* d_scale_b, const float* d_bias_b, double eps_b, int64_t B,
+                                   int64_t C, int64_t HW, float* d_y, void* stream);
 /* K18: max_pool2d(clamp_min(y, 0), (kh,kw), (sh,sw), (ph,pw)) of the same y in one pass, bit for bit what ATen's
  * max-pool writes (window clipped to the input, row-major scan, the last NaN of a window wins); no indices, no ceil_mode,
  * dilation 1.  d_x (B,C,H,W), d_y (B,C,OH,OW) with OH = (H + 2 ph - kh) / sh + 1.  k in {2,3}, s in {1,2}, p <= k / 2 per axis,
@@ -490,7 +498,7 @@ size_t sl_cosine_nt_ws_bytes(int64_t M, int64_t N, int64_t K);
 #define SL_PROF_GEMM 2   /* K6 cosine GEMM */
 #define SL_PROF_GATHER 3
 #define SL_PROF_SCORES 4
-#define SL_PROF_BATCHNORM 5 /* K16 fused inference BatchNorm */
+#define SL_PROF_BATCHNORM 5 /* K16 fused inference BatchNorm; launches = BatchNorm2d evaluations (K19) */
 #define SL_PROF_TOPK 6 /* K17 streaming fp32 top-k */
 #define SL_PROF_NFAM 7
 int sl_prof_enable(int on);

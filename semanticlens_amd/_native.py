@@ -115,6 +115,8 @@ SIGNATURES = {
     "sl_heat_boxes": (_int, [_vp, _i64, _i64, _i64, _int, ctypes.c_float, _vp, _vp, _sz, _vp]),
     "sl_batchnorm_infer": (_int, [_vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, ctypes.c_double, _int, _vp, _vp]),
     "sl_batchnorm_infer_add_relu": (_int, [_vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, ctypes.c_double, _vp, _vp]),
+    "sl_batchnorm_infer_add_bn_relu": (_int, [_vp, _vp, _vp, _vp, _vp, ctypes.c_double, _vp, _vp, _vp, _vp, _vp, ctypes.c_double, _i64, _i64,
+                                              _i64, _vp, _vp]),
     "sl_batchnorm_infer_relu_maxpool": (_int, [_vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, ctypes.c_double, _int, _int, _int,
                                                _int, _int, _int, _vp, _vp]),
     "sl_topk_init": (_int, [_vp, _vp, _i64, _i64, _vp]),
@@ -948,6 +950,31 @@ def batchnorm_infer(x: torch.Tensor, mean: torch.Tensor, var: torch.Tensor, weig
             rc = lib().sl_batchnorm_infer_add_relu(_ptr(x), _ptr(residual), B, C, H * W, _ptr(mean), _ptr(var), _ptr(weight),
                                                    _ptr(bias), float(eps), _ptr(out), _stream(x))
     _check(rc, "sl_batchnorm_infer")
+    return out
+
+
+BN_DUAL_MAX_CHANNELS = 2048  # two constant tables per block: half of BN_MAX_CHANNELS
+
+
+def batchnorm_infer_add_bn_relu(xa: torch.Tensor, bn_a, xb: torch.Tensor, bn_b) -> torch.Tensor:
+    """``relu_(F.batch_norm(xa, *bn_a) + F.batch_norm(xb, *bn_b))`` of two contiguous NCHW fp32 device tensors of one shape in one
+    pass, bit for bit (K19).  ``bn_a`` and ``bn_b`` are ``(mean, var, weight, bias, eps)``; ``xa`` is the left operand of the add.
+    Raises ``ValueError`` for what the entry point does not take (more than ``BN_DUAL_MAX_CHANNELS`` channels among it)."""
+    if xa.shape != xb.shape or xa.dim() != 4 or xa.device != xb.device:
+        raise ValueError(f"batchnorm_infer_add_bn_relu: two 4-D tensors of one shape and device expected, got {tuple(xa.shape)} and "
+                         f"{tuple(xb.shape)}")
+    B, C, H, W = xa.shape
+    for t in (xa, xb):
+        if t.dtype is not torch.float32 or not t.is_contiguous() or t.data_ptr() % 16:
+            raise ValueError("batchnorm_infer_add_bn_relu: inputs must be contiguous NCHW fp32, 16-byte aligned")
+    for p in (*bn_a[:4], *bn_b[:4]):
+        if p.dtype is not torch.float32 or p.device != xa.device or not p.is_contiguous() or p.numel() != C:
+            raise ValueError(f"batchnorm_infer_add_bn_relu: per-channel tensors must be contiguous fp32 of {C} elements on {xa.device}")
+    out = torch.empty_like(xa)
+    with _on(xa.device):
+        rc = lib().sl_batchnorm_infer_add_bn_relu(_ptr(xa), *(_ptr(p) for p in bn_a[:4]), float(bn_a[4]), _ptr(xb),
+                                                  *(_ptr(p) for p in bn_b[:4]), float(bn_b[4]), B, C, H * W, _ptr(out), _stream(xa))
+    _check(rc, "sl_batchnorm_infer_add_bn_relu")
     return out
 
 

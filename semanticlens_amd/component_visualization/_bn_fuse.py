@@ -9,6 +9,11 @@ the model is touched and outside the ``with`` block of :meth:`ActCache.hook_cont
   still called as modules and their hooks fire — and the patterns ``bn -> relu``, ``bn -> add(., other) -> relu`` and
   ``bn -> relu -> max_pool2d`` (the stem) are replaced by one fused call each.  A module that does not trace
   keeps its own ``forward``.
+* Where the ``other`` of ``bn -> add(., other) -> relu`` is the output of a plain ``nn.Sequential`` that ends in a plain
+  ``BatchNorm2d`` (the shortcut of a stage's first block) the owner gets a second graph: the Sequential's
+  leading children are called where the Sequential was, each as a module, and the tail is one call that normalises both
+  operands (``sl_batchnorm_infer_add_bn_relu``).  The owner runs that graph while nothing hooks the Sequential, its norm, the
+  traced norm or the activation and the Sequential's children are the traced ones, and the first graph otherwise.
 
 Eligibility is decided per call (``_eligible``): eval mode with running statistics and affine parameters, fp32 on a HIP device,
 NCHW-contiguous, grad mode off, MIOpen enabled, and for the fused patterns no hook on the norm or the activation, whose separate
@@ -53,6 +58,10 @@ def _plain_bn(m) -> bool:
 
 def _plain_relu(m) -> bool:
     return isinstance(m, nn.ReLU) and type(m).forward is nn.ReLU.forward
+
+
+def _plain_seq(m) -> bool:
+    return isinstance(m, nn.Sequential) and type(m).forward is nn.Sequential.forward
 
 
 def _plain_pool(m) -> bool:
@@ -159,6 +168,10 @@ class _Site:
         return ref
 
 
+def _bn_args(bn: nn.BatchNorm2d):
+    return bn.running_mean, bn.running_var, bn.weight, bn.bias, bn.eps
+
+
 def _bn_forward(site: _Site):
     def forward(x):
         if site.eligible(x):
@@ -188,6 +201,48 @@ class _Fused(nn.Module):
         return relu(out)
 
 
+class _FusedDual(nn.Module):
+    """``relu(add(bn(x), shortcut_bn(xb)))`` as one call: ``single`` is the fused tail of ``bn`` alone, ``seq`` the shortcut
+    ``nn.Sequential`` whose last child is ``shortcut.bn`` and whose leading children the graph has called to produce ``xb``."""
+
+    def __init__(self, single: _Fused, shortcut: _Site, seq: nn.Sequential):
+        super().__init__()
+        self.__dict__.update(single=single, shortcut=shortcut, seq=seq, children_seen=tuple(seq.children()), verified=set(),
+                             dropped=False)  # (not registered as children)
+
+    def ready(self) -> bool:
+        """What is known before the owner runs: the graph that bypasses ``seq.__call__`` may be taken."""
+        single, relu, now = self.single, self.single.relu, tuple(self.seq.children())
+        return (not self.dropped and not _hooked(self.seq) and not _hooked(self.shortcut.bn) and not _hooked(single.site.bn)
+                and not (isinstance(relu, nn.Module) and _hooked(relu)) and len(now) == len(self.children_seen)
+                and all(a is b for a, b in zip(now, self.children_seen)))
+
+    def forward(self, x, xb):
+        a, b = self.single.site, self.shortcut
+        if (self.ready() and a.eligible(x) and b.eligible(xb) and xb.shape == x.shape and xb.device == x.device
+                and x.shape[1] <= N.BN_DUAL_MAX_CHANNELS):
+            return self.run(x, xb)
+        return self.single(x, b.bn(xb))  # the shortcut's norm as a module, then the tail of the first graph
+
+    def run(self, x, xb):
+        bn_first = self.single.bn_first
+        left, right = ((x, self.single.site.bn), (xb, self.shortcut.bn)) if bn_first else ((xb, self.shortcut.bn), (x, self.single.site.bn))
+        out = N.batchnorm_infer_add_bn_relu(left[0], _bn_args(left[1]), right[0], _bn_args(right[1]))
+        key = ((x.shape[2] * x.shape[3]) % 4 == 0, bn_first)
+        if key in self.verified:
+            return out
+        ref = torch.relu_(F.batch_norm(left[0], *_bn_args(left[1])[:4], False, 0.0, left[1].eps)
+                          + F.batch_norm(right[0], *_bn_args(right[1])[:4], False, 0.0, right[1].eps))
+        if torch.equal(out.view(torch.int32), ref.view(torch.int32)):
+            self.verified.add(key)
+            return out
+        self.dropped = True
+        warnings.warn(
+            f"the fused BatchNorm + BatchNorm + add + ReLU kernel did not reproduce PyTorch's result bit for bit on {tuple(x.shape)} "
+            f"inputs; this shortcut's BatchNorm2d runs on its own from now on.", RuntimeWarning, stacklevel=3)
+        return ref
+
+
 class _FusedPool(nn.Module):
     """``max_pool2d(relu(bn(x)))`` as one call.  ``pool`` is the user's ``nn.MaxPool2d`` or, for ``F.max_pool2d`` with literal
     arguments, their dict.  A call that is not eligible runs ``inner`` (the fused ``relu(bn(x))``, which steps aside on its own
@@ -212,8 +267,9 @@ class _FusedPool(nn.Module):
         return pool(out) if isinstance(pool, nn.Module) else F.max_pool2d(out, **pool)
 
 
-def _trace(parent: nn.Module, sites: dict):
-    """GraphModule of ``parent``'s own forward with the fused patterns rewritten, or None."""
+def _trace(parent: nn.Module, sites: dict, dual: bool = False):
+    """GraphModule of ``parent``'s own forward with the fused patterns rewritten, or None.  ``dual``: also take a shortcut
+    Sequential's BatchNorm into the tail call; then ``(GraphModule, [its _FusedDual modules])``, or None when there is none."""
     from torch import fx
 
     class InplaceProxy(fx.Proxy):  # fx turns `a += b` into `a + b`; the graph must keep writing into `a`, which a caller may hold
@@ -263,14 +319,22 @@ def _trace(parent: nn.Module, sites: dict):
                 return given
         return None
 
-    n_fused = 0
+    def shortcut_of(node, add):
+        """The site of the trailing BatchNorm2d when ``node`` calls a plain Sequential whose only consumer is ``add``."""
+        seq = mods.get(node.target) if node.op == "call_module" else None
+        if not _plain_seq(seq) or node.kwargs or len(node.args) != 1 or set(node.users) != {add}:
+            return None
+        children = list(seq.children())
+        return sites.get(children[-1]) if len(children) >= 2 else None
+
+    n_fused, duals = 0, []
     for node in list(graph.nodes):
         if node.op != "call_module" or mods.get(node.target) not in sites or node.kwargs or len(node.args) != 1:
             continue
         if len(node.users) != 1:
             continue
         site, user = sites[mods[node.target]], next(iter(node.users))
-        last, fused, args = user, None, None
+        last, fused, args, stale = user, None, None, None
         if relu_of(user) is not None:
             fused, args = _Fused(site, relu_of(user)), (node.args[0],)
             follower = next(iter(user.users)) if len(user.users) == 1 else None  # the pool must be the ReLU's only consumer
@@ -286,7 +350,18 @@ def _trace(parent: nn.Module, sites: dict):
             if user.target is operator.iadd and not bn_first:
                 continue  # `other += bn(x)` writes into `other`, which the caller may hold: not the fused call's fresh tensor
             fused = _Fused(site, relu_of(last), user.target, bn_first)
-            args = (node.args[0], user.args[1] if bn_first else user.args[0])
+            other = user.args[1] if bn_first else user.args[0]
+            args = (node.args[0], other)
+            shortcut = shortcut_of(other, user) if dual else None
+            if shortcut is not None:
+                # the leading children where the Sequential was called (a block may run its shortcut before its first conv),
+                # each through its own __call__; only the BatchNorm moves into the tail
+                seq, tail = mods[other.target], other.args[0]
+                with graph.inserting_before(other):
+                    for child_name in list(seq._modules)[:-1]:
+                        tail = graph.call_module(f"{other.target}.{child_name}", (tail,))
+                fused, args, stale = _FusedDual(fused, shortcut, seq), (node.args[0], tail), other
+                duals.append(fused)
         if fused is None:
             continue
         name = f"_sl_fused_{n_fused}"
@@ -299,19 +374,24 @@ def _trace(parent: nn.Module, sites: dict):
         if last is not user:
             graph.erase_node(user)
         graph.erase_node(node)
-    if not n_fused:
+        if stale is not None:
+            graph.erase_node(stale)
+    if not n_fused or (dual and not duals):
         return None
     graph.lint()
     gm.recompile()
-    return gm
+    return (gm, duals) if dual else gm
 
 
-def _owner_forward(parent: nn.Module, gm, training: bool):
-    """The traced forward while the owner is in the mode it was traced in (a trace freezes `if self.training:`), its own otherwise."""
+def _owner_forward(parent: nn.Module, gm, training: bool, dual=None):
+    """The traced forward while the owner is in the mode it was traced in (a trace freezes `if self.training:`), its own otherwise.
+    ``dual``: the graph that also fuses a shortcut's BatchNorm and its ``_FusedDual`` modules; taken when all of them are ready."""
     own = type(parent).forward
 
     def forward(*args, **kwargs):
         if parent.training is training:
+            if dual is not None and all(f.ready() for f in dual[1]):
+                return dual[0].forward(*args, **kwargs)
             return gm.forward(*args, **kwargs)
         return own(parent, *args, **kwargs)
 
@@ -323,6 +403,7 @@ class _Plan:
         self.module_ids = tuple(id(m) for m in model.modules())
         self.sites = {m: _Site(m) for m in model.modules() if _plain_bn(m) and m is not model}
         self.parents: list = []  # (weak reference to the owner, GraphModule, the owner's training flag when it was traced)
+        self.duals: dict = {}  # index into `parents` -> (GraphModule with the shortcut's BatchNorm in the tail, its _FusedDual modules)
         for parent in model.modules():
             if "forward" in parent.__dict__ or not any(child in self.sites for child in parent.children()):
                 continue
@@ -330,8 +411,16 @@ class _Plan:
                 gm = _trace(parent, self.sites)
             except Exception:  # control flow on tensor values, *args, ...: this module keeps its own forward
                 gm = None
-            if gm is not None:
-                self.parents.append((weakref.ref(parent), gm, parent.training))
+            if gm is None:
+                continue
+            self.parents.append((weakref.ref(parent), gm, parent.training))
+            if any(_plain_seq(c) and len(c) >= 2 and c[-1] in self.sites for c in parent.children()):
+                try:
+                    dual = _trace(parent, self.sites, dual=True)
+                except Exception:
+                    dual = None
+                if dual is not None:
+                    self.duals[len(self.parents) - 1] = dual
 
     def valid_for(self, model: nn.Module) -> bool:
         return self.module_ids == tuple(id(m) for m in model.modules())
@@ -349,10 +438,10 @@ def substitute(model: nn.Module):
         if "forward" not in bn.__dict__:
             bn.forward = _bn_forward(site)
             swapped.append(bn)
-    for ref, gm, training in plan.parents:
+    for i, (ref, gm, training) in enumerate(plan.parents):
         parent = ref()
         if parent is not None and "forward" not in parent.__dict__:
-            parent.forward = _owner_forward(parent, gm, training)
+            parent.forward = _owner_forward(parent, gm, training, plan.duals.get(i))
             swapped.append(parent)
 
     def undo():

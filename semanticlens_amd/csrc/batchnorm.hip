@@ -3,7 +3,9 @@
 //   EPI_PLAIN     nothing
 //   EPI_RELU      clamp_min(y, 0)
 //   EPI_ADD_RELU  clamp_min(y + residual, 0)
-// HBM-bound: one read of x (and of the residual), one write of y.
+//   EPI_ADD_BN_RELU  clamp_min(y + y_b, 0), y_b the BatchNorm of a second tensor under its own constants: the tail of a stage's
+//                  first block, whose shortcut ends in a BatchNorm
+// HBM-bound: one read of x (and of the residual or the second tensor), one write of y.
 // K18 adds the stem's epilogue, max_pool2d(clamp_min(y, 0)): one read of x, one write of the pooled quarter;
 // neither the normalised tensor nor ATen's int64 indices go through memory.
 //
@@ -14,6 +16,11 @@
 //
 // Per-channel constants are read from the module's tensors on every launch and the inverse standard deviation is computed here:
 // every block builds a {mean, inv_std, scale, bias} table of the C channels in LDS (C <= 4096), nothing survives the launch.
+// EPI_ADD_BN_RELU keeps two such tables, one behind the other, and takes C <= 2048: the same 64 KiB.
+//
+// SL_PROF_BATCHNORM counts BatchNorm2d evaluations, so a call of EPI_ADD_BN_RELU leaves two records in the slot: the kernel's
+// (its time, 3 x total x 4 bytes) and an empty one (work 0, its two events recorded back to back on the stream).  The slot's
+// time and bytes are the kernels'; its time over its count is not a per-launch average.
 #include "common.hpp"
 
 namespace sl {
@@ -21,12 +28,15 @@ namespace {
 
 typedef float f4 __attribute__((ext_vector_type(4)));
 
-enum { EPI_PLAIN = 0, EPI_RELU = 1, EPI_ADD_RELU = 2 };
+enum { EPI_PLAIN = 0, EPI_RELU = 1, EPI_ADD_RELU = 2, EPI_ADD_BN_RELU = 3 };
 enum { POL_PLAIN = 0, POL_NT_STORE = 1, POL_NT_BOTH = 2 };
 
 constexpr int kBlock = 256;
 constexpr int kUnroll = 4;         // 16-byte pieces per lane in flight
 constexpr int64_t kMaxC = 4096;    // 64 KiB of LDS for the table
+constexpr int64_t kMaxCDual = 2048;  // EPI_ADD_BN_RELU: two tables in the same 64 KiB
+constexpr int64_t kLdsPerCu = 160 * 1024;
+constexpr size_t kDualResidentFrom = 32 * 1024;  // EPI_ADD_BN_RELU: above this many bytes of tables the grid is the resident blocks
 constexpr int64_t kMaxTotal = (int64_t)1 << 31;
 
 // MIOpen's form: the estimate is added in fp32 and the root is the hardware's v_rsq_f32 (not a divide by a square root, not the
@@ -42,10 +52,28 @@ __device__ inline float bn_value(float x, const f4 k) {
 // ATen's clamp_min functor: NaN passes through with its bits, max(-0.0, 0) is +0.0
 __device__ inline float relu_clamp(float v) { return v != v ? v : fmaxf(v, 0.f); }
 
+// a + b as ATen's add kernel computes it.  Only two NaN operands tell the forms apart: the hardware returns one operand's payload,
+// which one depends on the instruction and on the operand's position, and the compiler is free to commute an add or to pair
+// two of them into a packed one (it did: v_pk_add_f32 kept the other payload in every such element, whichever tensor was the
+// left operand).  So the instruction is written out, with the right-hand operand first: the form that matched on the device.
+__device__ inline float add_as_aten(float a, float b) {
+  float r;
+  asm("v_add_f32_e32 %0, %1, %2" : "=v"(r) : "v"(b), "v"(a));
+  return r;
+}
+
+// One BatchNorm2d's per-channel tensors, as the module holds them.
+struct BnParams {
+  const float *mean, *var, *scale, *bias;
+  double eps;
+};
+
+// r is the residual (EPI_ADD_RELU) or the second tensor's element, kb its constants (EPI_ADD_BN_RELU)
 template <int EPI>
-__device__ inline float bn_finish(float x, const f4 k, float r) {
+__device__ inline float bn_finish(float x, const f4 k, float r, const f4 kb) {
   float y = bn_value(x, k);
   if constexpr (EPI == EPI_ADD_RELU) y = y + r;  // y is an fp32 value here, as when it went through memory
+  if constexpr (EPI == EPI_ADD_BN_RELU) y = add_as_aten(y, bn_value(r, kb));  // two fp32 values; x's is the left operand, as in the model
   if constexpr (EPI != EPI_PLAIN) y = relu_clamp(y);
   return y;
 }
@@ -78,15 +106,20 @@ __device__ inline void st1(float* p, float v) {
 // ALIGNED: HW % 4 == 0, a 16-byte piece never leaves its (n, c) plane.  Pieces are dealt to waves in runs of 64 * kUnroll; a run
 // of 64 pieces that lies inside one plane takes its constants once (a wave-uniform LDS read), every other run looks its channel
 // up per lane.  Without ALIGNED (HW = 49) a piece may cross planes: the channel is advanced element by element.
+// EPI_ADD_BN_RELU: `res` is the second tensor, `b` its BatchNorm, and tab[C + c] holds b's constants of channel c.
 template <int EPI, bool ALIGNED, int POL>
 __global__ __launch_bounds__(kBlock) void batchnorm_kernel(const float* __restrict__ x, const float* __restrict__ res,
-                                                           float* __restrict__ y, const float* __restrict__ mean,
-                                                           const float* __restrict__ var, const float* __restrict__ scale,
-                                                           const float* __restrict__ bias, double eps, uint32_t C, uint32_t HW,
-                                                           uint32_t total) {
+                                                           float* __restrict__ y, const BnParams a, const BnParams b, uint32_t C,
+                                                           uint32_t HW, uint32_t total) {
+  constexpr bool HAS_RES = EPI == EPI_ADD_RELU || EPI == EPI_ADD_BN_RELU;
+  constexpr bool DUAL = EPI == EPI_ADD_BN_RELU;
   extern __shared__ f4 tab[];
-  for (uint32_t c = threadIdx.x; c < C; c += kBlock) tab[c] = f4{mean[c], bn_inv_std(var[c], eps), scale[c], bias[c]};
+  for (uint32_t c = threadIdx.x; c < C; c += kBlock) {
+    tab[c] = f4{a.mean[c], bn_inv_std(a.var[c], a.eps), a.scale[c], a.bias[c]};
+    if constexpr (DUAL) tab[C + c] = f4{b.mean[c], bn_inv_std(b.var[c], b.eps), b.scale[c], b.bias[c]};
+  }
   __syncthreads();
+  const uint32_t second = DUAL ? C : 0u;  // tab[second + c]: the second tensor's constants (unused otherwise)
 
   const uint32_t lane = threadIdx.x & 63;
   const uint32_t wave = blockIdx.x * (kBlock / 64) + (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -105,7 +138,7 @@ __global__ __launch_bounds__(kBlock) void batchnorm_kernel(const float* __restri
       const uint32_t i = base + u * 64 + lane;
       if (i < n4) {
         v[u] = ld4<POL>(x4 + i);
-        if constexpr (EPI == EPI_ADD_RELU) r[u] = ld4<POL>(r4 + i);
+        if constexpr (HAS_RES) r[u] = ld4<POL>(r4 + i);
       }
     }
 #pragma unroll
@@ -122,9 +155,9 @@ __global__ __launch_bounds__(kBlock) void batchnorm_kernel(const float* __restri
         else
           c = (i < n4 ? i / per_plane : 0u) % C;
         if (i < n4) {
-          const f4 k = tab[c];
+          const f4 k = tab[c], kb = tab[second + c];
 #pragma unroll
-          for (int j = 0; j < 4; ++j) o[j] = bn_finish<EPI>(v[u][j], k, EPI == EPI_ADD_RELU ? r[u][j] : 0.f);
+          for (int j = 0; j < 4; ++j) o[j] = bn_finish<EPI>(v[u][j], k, HAS_RES ? r[u][j] : 0.f, kb);
         }
       } else {
         if (i < n4) {
@@ -132,7 +165,7 @@ __global__ __launch_bounds__(kBlock) void batchnorm_kernel(const float* __restri
           uint32_t off = e - p * HW, c = p % C;
 #pragma unroll
           for (int j = 0; j < 4; ++j) {
-            o[j] = bn_finish<EPI>(v[u][j], tab[c], EPI == EPI_ADD_RELU ? r[u][j] : 0.f);
+            o[j] = bn_finish<EPI>(v[u][j], tab[c], HAS_RES ? r[u][j] : 0.f, tab[second + c]);
             if (++off == HW) {
               off = 0;
               if (++c == C) c = 0;
@@ -146,16 +179,16 @@ __global__ __launch_bounds__(kBlock) void batchnorm_kernel(const float* __restri
   // the last total % 4 elements (none when HW % 4 == 0)
   if (blockIdx.x == 0 && threadIdx.x < (total & 3u)) {
     const uint32_t e = (total & ~3u) + threadIdx.x;
-    y[e] = bn_finish<EPI>(x[e], tab[(e / HW) % C], EPI == EPI_ADD_RELU ? res[e] : 0.f);
+    const uint32_t c = (e / HW) % C;
+    y[e] = bn_finish<EPI>(x[e], tab[c], HAS_RES ? res[e] : 0.f, tab[second + c]);
   }
 }
 
 template <int EPI, bool ALIGNED>
 void launch_policy(ProfScope& prof, int pol, dim3 grid, size_t lds, hipStream_t st, const float* x, const float* res, float* y,
-                   const float* mean, const float* var, const float* scale, const float* bias, double eps, uint32_t C,
-                   uint32_t HW, uint32_t total) {
+                   const BnParams& a, const BnParams& b, uint32_t C, uint32_t HW, uint32_t total) {
 #define SL_BN_LAUNCH(P_) \
-  SL_LAUNCH(prof, (batchnorm_kernel<EPI, ALIGNED, P_>), grid, dim3(kBlock), lds, st, x, res, y, mean, var, scale, bias, eps, C, HW, total)
+  SL_LAUNCH(prof, (batchnorm_kernel<EPI, ALIGNED, P_>), grid, dim3(kBlock), lds, st, x, res, y, a, b, C, HW, total)
   switch (pol) {
     case POL_PLAIN: SL_BN_LAUNCH(POL_PLAIN); break;
     case POL_NT_STORE: SL_BN_LAUNCH(POL_NT_STORE); break;
@@ -175,39 +208,53 @@ int bn_policy(int64_t tensor_bytes) {
   return pol;
 }
 
-int launch_batchnorm(int epi, const float* x, const float* res, float* y, const float* mean, const float* var,
-                     const float* scale, const float* bias, double eps, int64_t B, int64_t C, int64_t HW, hipStream_t st,
-                     const char* who) {
+int launch_batchnorm(int epi, const float* x, const float* res, float* y, const BnParams& a, const BnParams& b, int64_t B,
+                     int64_t C, int64_t HW, hipStream_t st, const char* who) {
+  const bool dual = epi == EPI_ADD_BN_RELU;
   SL_REQUIRE(B >= 0 && C >= 0 && HW >= 0, "%s: negative shape", who);
   const int64_t total = B * C * HW;
   if (total == 0) return 0;
-  SL_REQUIRE(x && y && mean && var && scale && bias && (epi != EPI_ADD_RELU || res), "%s: null pointer", who);
-  SL_REQUIRE(C <= kMaxC, "%s: %lld channels exceed the supported maximum of %lld", who, (long long)C, (long long)kMaxC);
+  SL_REQUIRE(x && y && a.mean && a.var && a.scale && a.bias && (epi < EPI_ADD_RELU || res), "%s: null pointer", who);
+  SL_REQUIRE(!dual || (b.mean && b.var && b.scale && b.bias), "%s: null pointer", who);
+  const int64_t max_c = dual ? kMaxCDual : kMaxC;
+  SL_REQUIRE(C <= max_c, "%s: %lld channels exceed the supported maximum of %lld", who, (long long)C, (long long)max_c);
   SL_REQUIRE(total < kMaxTotal, "%s: %lld elements exceed the supported maximum of 2^31 - 1", who, (long long)total);
   SL_REQUIRE((((uintptr_t)x | (uintptr_t)y | (uintptr_t)res) & 15) == 0, "%s: tensors must be 16-byte aligned", who);
-  const int passes = epi == EPI_ADD_RELU ? 3 : 2;
+  const int passes = epi >= EPI_ADD_RELU ? 3 : 2;
   ProfScope prof(SL_PROF_BATCHNORM, st, (double)total * 4 * passes);
   const int pol = bn_policy(total * 4);
+  const size_t lds = (size_t)C * sizeof(f4) * (dual ? 2 : 1);
   const int64_t per_block = (int64_t)kBlock * kUnroll * 4;
   int64_t blocks = (total + per_block - 1) / per_block;
-  const int64_t cap = (int64_t)num_cus() * 8;
+  int64_t per_cu = 8;
+  // every block builds both tables, 40 bytes read and two v_rsq_f32 per channel.  Above 32 KiB of tables (C > 1024) the grid
+  // is the blocks resident at once (two per CU at C = 2048), so that a CU builds them once per resident block and not once
+  // per round: 80 against 84 us at (256, 2048, 7, 7).  At 32 KiB, where five blocks are resident, the same cut cost 128
+  // against 105 us at (256, 1024, 14, 14), so up to there the grid stays at 8 blocks per CU.
+  if (dual && lds > kDualResidentFrom) per_cu = kLdsPerCu / (int64_t)lds;
+  const int64_t cap = (int64_t)num_cus() * per_cu;
   if (blocks > cap) blocks = cap;
   const dim3 grid((unsigned)blocks);
-  const size_t lds = (size_t)C * sizeof(f4);
-#define SL_BN_EPI(E_)                                                                                                      \
-  if (HW % 4 == 0)                                                                                                         \
-    launch_policy<E_, true>(prof, pol, grid, lds, st, x, res, y, mean, var, scale, bias, eps, (uint32_t)C, (uint32_t)HW,   \
-                            (uint32_t)total);                                                                              \
-  else                                                                                                                     \
-    launch_policy<E_, false>(prof, pol, grid, lds, st, x, res, y, mean, var, scale, bias, eps, (uint32_t)C, (uint32_t)HW,  \
-                             (uint32_t)total)
+#define SL_BN_EPI(E_)                                                                                                \
+  if (HW % 4 == 0)                                                                                                   \
+    launch_policy<E_, true>(prof, pol, grid, lds, st, x, res, y, a, b, (uint32_t)C, (uint32_t)HW, (uint32_t)total);  \
+  else                                                                                                               \
+    launch_policy<E_, false>(prof, pol, grid, lds, st, x, res, y, a, b, (uint32_t)C, (uint32_t)HW, (uint32_t)total)
   switch (epi) {
     case EPI_PLAIN: SL_BN_EPI(EPI_PLAIN); break;
     case EPI_RELU: SL_BN_EPI(EPI_RELU); break;
-    default: SL_BN_EPI(EPI_ADD_RELU); break;
+    case EPI_ADD_RELU: SL_BN_EPI(EPI_ADD_RELU); break;
+    default: SL_BN_EPI(EPI_ADD_BN_RELU); break;
   }
 #undef SL_BN_EPI
   SL_CHECK_HIP(hipGetLastError());
+  if (dual) {  // the second BatchNorm2d of this call: a record of its own with no work and no time (see the head of the file)
+    ProfScope second(SL_PROF_BATCHNORM, st, 0.0);
+    if (second.start) {
+      SL_CHECK_HIP(hipEventRecord(second.start, st));
+      SL_CHECK_HIP(hipEventRecord(second.stop, st));
+    }
+  }
   return 0;
 }
 
@@ -221,7 +268,6 @@ int launch_batchnorm(int epi, const float* x, const float* res, float* y, const 
 // and `v > max || isnan(v)` replaces it, so a window with NaNs yields the last one in scan order, payload included.  Positions
 // outside the input read as -inf here, which that rule never selects (every window holds at least one real element: p <= k / 2).
 constexpr int64_t kPoolLds = 64 * 1024;  // staged rows per block
-constexpr int64_t kLdsPerCu = 160 * 1024;
 constexpr int64_t kPoolMaxW = 4096;      // so that kh <= 3 rows always fit
 
 struct PoolGeom {
@@ -450,15 +496,24 @@ using namespace sl;
 
 SL_API int sl_batchnorm_infer(const float* d_x, int64_t B, int64_t C, int64_t HW, const float* d_mean, const float* d_var,
                               const float* d_scale, const float* d_bias, double eps, int relu, float* d_y, void* stream) {
-  return launch_batchnorm(relu ? EPI_RELU : EPI_PLAIN, d_x, nullptr, d_y, d_mean, d_var, d_scale, d_bias, eps, B, C, HW,
-                          (hipStream_t)stream, "sl_batchnorm_infer");
+  return launch_batchnorm(relu ? EPI_RELU : EPI_PLAIN, d_x, nullptr, d_y, BnParams{d_mean, d_var, d_scale, d_bias, eps}, BnParams{},
+                          B, C, HW, (hipStream_t)stream, "sl_batchnorm_infer");
 }
 
 SL_API int sl_batchnorm_infer_add_relu(const float* d_x, const float* d_residual, int64_t B, int64_t C, int64_t HW,
                                        const float* d_mean, const float* d_var, const float* d_scale, const float* d_bias,
                                        double eps, float* d_y, void* stream) {
-  return launch_batchnorm(EPI_ADD_RELU, d_x, d_residual, d_y, d_mean, d_var, d_scale, d_bias, eps, B, C, HW, (hipStream_t)stream,
-                          "sl_batchnorm_infer_add_relu");
+  return launch_batchnorm(EPI_ADD_RELU, d_x, d_residual, d_y, BnParams{d_mean, d_var, d_scale, d_bias, eps}, BnParams{}, B, C, HW,
+                          (hipStream_t)stream, "sl_batchnorm_infer_add_relu");
+}
+
+SL_API int sl_batchnorm_infer_add_bn_relu(const float* d_xa, const float* d_mean_a, const float* d_var_a, const float* d_scale_a,
+                                          const float* d_bias_a, double eps_a, const float* d_xb, const float* d_mean_b,
+                                          const float* d_var_b, const float* d_scale_b, const float* d_bias_b, double eps_b,
+                                          int64_t B, int64_t C, int64_t HW, float* d_y, void* stream) {
+  return launch_batchnorm(EPI_ADD_BN_RELU, d_xa, d_xb, d_y, BnParams{d_mean_a, d_var_a, d_scale_a, d_bias_a, eps_a},
+                          BnParams{d_mean_b, d_var_b, d_scale_b, d_bias_b, eps_b}, B, C, HW, (hipStream_t)stream,
+                          "sl_batchnorm_infer_add_bn_relu");
 }
 
 SL_API int sl_batchnorm_infer_relu_maxpool(const float* d_x, int64_t B, int64_t C, int64_t H, int64_t W, const float* d_mean,
