@@ -351,7 +351,8 @@ int cosine_matrix_multi(const float* X, int64_t Q, int64_t K, const float* const
   // fp32-MFMA mode: the layers are gathered into ONE (sum C, K) fp32 operand when that lets the 256 x 256 8-phase kernel
   // run (rows of whole 128-byte lines, enough tiles to fill the chip): 12 launches of 120 tiles become one of 1440
   const bool fused_f32 = !fast && L > 1 && L <= kMaxFusedLayers && K % 32 == 0 && K > 0 && ((uintptr_t)X & 15) == 0 &&
-                         gemm8::fits(Q, csum, K * 4) && gemm8::worth_it(Q, csum) && !gemm8::worth_it(Q, cmax);
+                         gemm_choice::fits(Q, csum, K * 4) && gemm_choice::worth_it(Q, csum, num_cus()) &&
+                         !gemm_choice::worth_it(Q, cmax, num_cus());
   const int64_t yrows = (fused || fused_f32) ? csum : cmax;  // rows of the y scratch (all layers, or one at a time)
   float* rx = (float*)ws;
   float* ry = (float*)(ws + align256_((size_t)Q * 4));

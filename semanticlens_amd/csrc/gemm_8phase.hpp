@@ -28,10 +28,7 @@
 //   read slot, before its barrier (the guide's "read one phase after the wait"): phase 2 waits vmcnt(8) (A1 of this
 //   stage; four younger pieces may fly), phases 3 and 4 vmcnt(6) (B0/B1, then A0 of the next stage).  Raw s_barrier
 //   only: __syncthreads() would add vmcnt(0) and drain the ring.
-// * LDS image: unpadded 128-byte rows, 16-byte slots XOR-swizzled by (row >> 1) & 7 on the DMA's SOURCE address and on
-//   the fragment read: conflict-free ds_read_b128.
-// * One tile per workgroup; tile order: every XCD gets a contiguous range of tiles, walked in bands of four tile rows, so the workgroups that
-//   share an L2 share A and B panels (+2-3 % here).
+// * LDS image, swizzle and the XCD-aware tile order (one tile per workgroup): gemm_ring.hpp.
 // * Interior tiles store without per-element predicates (the predicated epilogue was VALU-bound: 10.4 K vs 4.6 K cycles).
 // Per output element the products are accumulated in the same order as in the 128 x 128 kernels of gemm_bf16x3.hpp /
 // gemm_f32.hpp: results are bit-identical to theirs (tests/test_gpu_parity.py::test_gemm_tile_variants_are_bit_identical).
@@ -40,19 +37,15 @@
 // algorithmic = 1.36 PFLOP/s of bf16 MFMA work issued; in-tile matrix-pipe duty 0.88 at a shader clock of 1.70 GHz (the
 // part is power-limited: the 256 x 128 kernel runs 0.60 duty at 2.0 GHz).
 #pragma once
-#include "common.hpp"
-#include "gemm_epilogue.hpp"
+#include "gemm_ring.hpp"
 
 namespace sl {
 namespace gemm8 {
 
-typedef float floatx16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+using ring::IntC;
+using ring::raw_barrier;
+using ring::static_for;
 typedef float f32x4 __attribute__((ext_vector_type(4)));
-// One 16-byte fragment register quad, either mode.  It must be an ext_vector type: read through HIP's struct `uint4`, hipcc
-// (ROCm 7.2) cannot tell the fragment reads from the LDS-DMA writes apart and puts `s_waitcnt vmcnt(0)` in front of the
-// first ds_read of every phase, which drains the ring (455 instead of 407 cycles per slot).
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int MODE_BF16X3 = 0, MODE_F32 = 1;
 constexpr int BM = 256, BN = 256;
@@ -60,13 +53,6 @@ constexpr int IMG_BYTES = 256 * 128;        // one operand of one stage: 32 KB
 constexpr int STAGE_BYTES = 2 * IMG_BYTES;  // A image, B image
 constexpr int LOOK = 6;                     // pieces issued ahead of the phase that runs
 
-template <int N_>
-struct IntC {
-  static constexpr int value = N_;
-};
-
-// An epilogue that reads memory per element (LinearEpi with a residual / positional table) exposes
-// `static constexpr bool kFetches = true`, `fetch(row, col)` and `store_fetched(row, col, acc, column, fetched)`.
 __device__ __forceinline__ void wait_vm_pieces(int n) {  // at most n pieces (2 loads each) of this wave still in flight
   switch (n) {
     case 0: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
@@ -90,20 +76,7 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_8phase_kernel(const unsigned c
   const int wr = w >> 2, wc = w & 3;
   const int li = lane & 31, lh = lane >> 5;
   int tm_i, tn_i;
-  {  // XCD-aware tile order (bijective for any grid): XCD x = blockIdx % 8 owns a contiguous range of tiles, walked in
-     // bands of GROUP_M tile rows so that the workgroups sharing an L2 share A and B panels
-    const int nwg = tiles_m * tiles_n;
-    const int xcd = blockIdx.x & 7, idx = blockIdx.x >> 3;
-    const int q = nwg >> 3, r = nwg & 7;
-    const int tile = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-    constexpr int GROUP_M = 4;
-    const int band = tile / (GROUP_M * tiles_n);
-    const int first_m = band * GROUP_M;
-    const int rows = tiles_m - first_m < GROUP_M ? tiles_m - first_m : GROUP_M;
-    const int in_band = tile - band * GROUP_M * tiles_n;
-    tm_i = first_m + in_band % rows;
-    tn_i = in_band / rows;
-  }
+  ring::xcd_tile(tiles_m, tiles_n, tm_i, tn_i);
   const int64_t m0 = (int64_t)tm_i * BM;
   const int64_t n0 = (int64_t)tn_i * BN;
 #ifdef SL_GEMM_CLOCKPROBE  // tools/native/gemm3_lab.hip
@@ -111,18 +84,11 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_8phase_kernel(const unsigned c
   unsigned long long probe_c1 = 0, probe_c2 = 0;
 #endif
 
-  floatx16 acc[4][2];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
+  floatx16 acc[4][2] = {};
 
   // ---- LDS-DMA plan.  Piece q of a stage: 0 = B rows 0-127, 1 = B rows 128-255, 2 = A rows {0-63, 128-191} (ih = 0 of
   // both wave groups), 3 = A rows {64-127, 192-255}.  Wave w moves row groups 2 w and 2 w + 1 (8 rows each) of a piece.
-  // Lane L lands in row L >> 3 of its group, slot L & 7, and fetches chunk (L & 7) ^ ((row >> 1) & 7) of the row's line.
-  uint32_t src[4][2];  // byte offset of this lane's chunk in the first k-tile (operands < 4 GB: checked by launch())
+  uint32_t src[4][2];  // ring::dma_src of the group's row lane >> 3
   int dst[4][2];       // wave-uniform LDS byte offset of the row group inside a stage
 #pragma unroll
   for (int q = 0; q < 4; ++q)
@@ -133,17 +99,15 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_8phase_kernel(const unsigned c
       if (q < 2) row0 = q * 128 + rg * 8;
       else row0 = (rg < 8 ? rg * 8 : 128 + (rg - 8) * 8) + (q - 2) * 64;
       const int row = row0 + (lane >> 3);
-      const int chunk = (lane & 7) ^ ((row >> 1) & 7);
+      const int chunk = ring::dma_chunk(lane, row);
       if (q < 2) {
-        src[q][g] = (uint32_t)((n0 + row < N ? n0 + row : N - 1) * row_bytes + chunk * 16);  // rows past the edge are clamped (never stored)
+        src[q][g] = ring::dma_src(n0, row, N, row_bytes, chunk);
         dst[q][g] = IMG_BYTES + row0 * 128;
       } else {
-        src[q][g] = (uint32_t)((m0 + row < M ? m0 + row : M - 1) * row_bytes + chunk * 16);
+        src[q][g] = ring::dma_src(m0, row, M, row_bytes, chunk);
         dst[q][g] = row0 * 128;
       }
     }
-  typedef __attribute__((address_space(3))) void lds_void;
-  typedef const __attribute__((address_space(1))) void glb_void;
   const int npieces = ns * 4;
   // instruction g of piece n = 4 stage + q -> ring slot (stage & 1, q)
   auto issue = [&](int stage, auto Qc, int g) __attribute__((always_inline)) {
@@ -151,7 +115,7 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_8phase_kernel(const unsigned c
     // wave-uniform base (SGPR pair) + 32-bit lane offset: the saddr form of global_load_lds, no 64-bit VALU address math
     const unsigned char* base = (q < 2 ? B : A) + (int64_t)stage * 128;
     unsigned char* l = smem + (stage & 1) * STAGE_BYTES;
-    __builtin_amdgcn_global_load_lds((glb_void*)(base + src[q][g]), (lds_void*)(l + dst[q][g]), 16, 0, 0);
+    ring::dma16(base + src[q][g], l + dst[q][g]);
   };
 
   // ---- fragment addresses (first 16-byte chunk this lane reads in a stage; the others are XORs of it)
@@ -162,24 +126,19 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_8phase_kernel(const unsigned c
   for (int t = 0; t < 4; ++t) {
     const int ar = wr * 128 + t * 32 + li;
     const int c0 = MODE == MODE_BF16X3 ? lh : 4 * lh;
-    a_addr[t] = ar * 128 + ((c0 ^ ((ar >> 1) & 7)) << 4);
+    a_addr[t] = ar * 128 + ((c0 ^ ring::swz(ar)) << 4);
   }
 #pragma unroll
   for (int t = 0; t < 2; ++t) {
     const int br = wc * 64 + t * 32 + li;
     const int c0 = MODE == MODE_BF16X3 ? lh : 4 * lh;
-    b_addr[t] = IMG_BYTES + br * 128 + ((c0 ^ ((br >> 1) & 7)) << 4);
+    b_addr[t] = IMG_BYTES + br * 128 + ((c0 ^ ring::swz(br)) << 4);
   }
   // fragments: [k-half][column tile][0|1] and [row tile of the phase][0|1]; the last index is hi / lo (bf16x3) or the
   // two float4 of the k-half (f32).  uint4 carries either.
   u32x4 fb[2][2][2], fa[2][2];
   constexpr int SUB = MODE == MODE_BF16X3 ? 64 : 16;  // address XOR between the two fragments of a (tile, k-half)
 
-  auto raw_barrier = [&]() __attribute__((always_inline)) {
-    __builtin_amdgcn_sched_barrier(0);
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_sched_barrier(0);
-  };
   // one phase; P = 1..4, TAIL: the stage is one of the last two (pieces to issue may not exist, waits are exact)
   auto phase = [&](int stage, auto Pc, auto Tc) __attribute__((always_inline)) {
     constexpr int P = decltype(Pc)::value;
@@ -295,22 +254,8 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_8phase_kernel(const unsigned c
   // waits for the acknowledgement of all 128 stores per lane, ~10 K cycles a dying workgroup never pays.)
   if (ns > 0) {
     // prologue ("phase 0"): pieces 0..LOOK, then B0, B1, A0 of stage 0 must have landed
-#pragma unroll
-    for (int g = 0; g < 2; ++g) issue(0, IntC<0>(), g);
-#pragma unroll
-    for (int g = 0; g < 2; ++g) issue(0, IntC<1>(), g);
-#pragma unroll
-    for (int g = 0; g < 2; ++g) issue(0, IntC<2>(), g);
-#pragma unroll
-    for (int g = 0; g < 2; ++g) issue(0, IntC<3>(), g);
-    if (ns > 1) {
-#pragma unroll
-      for (int g = 0; g < 2; ++g) issue(1, IntC<0>(), g);
-#pragma unroll
-      for (int g = 0; g < 2; ++g) issue(1, IntC<1>(), g);
-#pragma unroll
-      for (int g = 0; g < 2; ++g) issue(1, IntC<2>(), g);
-    }
+    static_for<0, 4>([&](auto Qc) __attribute__((always_inline)) { issue(0, Qc, 0), issue(0, Qc, 1); });
+    if (ns > 1) static_for<0, 3>([&](auto Qc) __attribute__((always_inline)) { issue(1, Qc, 0), issue(1, Qc, 1); });
     wait_vm_pieces(ns > 1 ? LOOK - 2 : 1);
     raw_barrier();
 #ifdef SL_GEMM_CLOCKPROBE
@@ -359,37 +304,14 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_8phase_kernel(const unsigned c
 #endif
 }
 
-inline int64_t tiles_of(int64_t M, int64_t N) { return ((M + BM - 1) / BM) * ((N + BN - 1) / BN); }
-// lane offsets are 32-bit
-inline bool fits(int64_t M, int64_t N, int64_t row_bytes) { return (M > N ? M : N) * row_bytes < (1ll << 32); }
-
 // rows of `row_bytes` bytes (16-byte aligned, as the bases), ns = k-tiles of 32 (128-byte lines) per row
 template <int MODE, class Epi>
 int launch(ProfScope& prof, const void* A, int64_t M, const void* B, int64_t N, int64_t row_bytes, int64_t ns, const Epi& epi,
            hipStream_t st) {
-  const int64_t tm = (M + BM - 1) / BM, tn = (N + BN - 1) / BN;
-  SL_REQUIRE(tm * tn < (1ll << 31) && ns < (1ll << 29), "GEMM: too many tiles");
-  SL_REQUIRE(fits(M, N, row_bytes), "GEMM: operand larger than 4 GB (use another kernel)");
-  if (tm * tn == 0) return 0;
-  SL_LAUNCH(prof, (gemm_nt_8phase_kernel<MODE, Epi>), dim3((unsigned)(tm * tn)), dim3(512), 0, st, (const unsigned char*)A,
-            (const unsigned char*)B, M, N, row_bytes, (int)ns, (int)tm, (int)tn, epi);
-  SL_CHECK_HIP(hipGetLastError());
-  return 0;
-}
-
-// kernel choice shared by the bf16x3 and the f32 launchers: the 8-phase kernel from half a tile per CU upwards (the encoder's
-// 150-600-tile GEMMs gain, ViT-B/32 image encode 9.66 -> 9.08 ms)
-inline bool worth_it(int64_t M, int64_t N) { return tiles_of(M, N) * 2 >= (int64_t)num_cus(); }
-
-// fp32-input MFMA mode: a tile takes 5.3x longer than in bf16x3 mode and the 128 x 128 kernel reaches 0.76-0.83 of peak on
-// its own, so the big kernel only pays when its last round is nearly full or there is a single round
-// (tools/native/gemm3_lab, K = 1152: 150 tiles 84 vs 79 TFLOP/s, 600 tiles 112 vs 120, 1280 tiles 140 vs 126, 1440 tiles
-// 132 vs 123).
-inline bool worth_it_f32(int64_t M, int64_t N) {
-  if (!worth_it(M, N)) return false;
-  const int64_t t = tiles_of(M, N), cus = num_cus();
-  const int64_t rounds = (t + cus - 1) / cus;
-  return rounds == 1 || t * 10 >= rounds * cus * 9;
+  return ring::launch_tiles(M, N, BM, BN, row_bytes, ns, [&](int64_t tm, int64_t tn) {
+    SL_LAUNCH(prof, (gemm_nt_8phase_kernel<MODE, Epi>), dim3((unsigned)(tm * tn)), dim3(512), 0, st, (const unsigned char*)A,
+              (const unsigned char*)B, M, N, row_bytes, (int)ns, (int)tm, (int)tn, epi);
+  });
 }
 
 }  // namespace gemm8

@@ -21,17 +21,13 @@
 // A and B fragments are read with the same (lane>>5)*8 + j k-pattern, so the result does not depend on how the
 // hardware orders k inside a fragment.
 #pragma once
-#include "common.hpp"
+#include "gemm_ring.hpp"
 #include "gemm_8phase.hpp"
 #include "gemm_w4.hpp"
 #include "gemm_skinny.hpp"
-#include <cstdlib>
 
 namespace sl {
 namespace gemm3 {
-
-typedef float floatx16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 constexpr int BM = 128, BN = 128, BK = 32;
 constexpr int ROW_BYTES = 80;                 // 64 data + 16 pad
@@ -84,12 +80,9 @@ static __global__ __launch_bounds__(256) void split_bf16_kernel(const float* __r
 
 // ---- kernel 1: 128 x 128 tiles staged through registers ----------------------------------------------------------
 // Epi: same contract as gemm_f32.hpp (column(col), store(row, col, acc, colval))
-#ifndef SL_G3_WAVES
-#define SL_G3_WAVES 2
-#endif
 template <class Epi>
-__global__ __launch_bounds__(256, SL_G3_WAVES) void gemm3_nt_kernel(const uint16_t* __restrict__ A, const uint16_t* __restrict__ B,
-                                                                    int64_t M, int64_t N, int64_t Kp, int tiles_n, Epi epi) {
+__global__ __launch_bounds__(256, 2) void gemm3_nt_kernel(const uint16_t* __restrict__ A, const uint16_t* __restrict__ B,
+                                                        int64_t M, int64_t N, int64_t Kp, int tiles_n, Epi epi) {
   __shared__ __align__(16) unsigned char smem[4 * IMG_BYTES];  // A_hi | A_lo | B_hi | B_lo
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -339,9 +332,6 @@ __global__ __launch_bounds__(256, 2) void gemm3_nt_dma256_kernel(const uint16_t*
 #endif
 }
 
-// (kernel 3, the 256 x 256 ping-pong kernel of round 2, was superseded by gemm_8phase.hpp and lives in
-// tools/native/gemm3_pingpong_lab.hpp for the lab harness; no dispatch of the library reaches it.)
-
 inline int launch_split(const float* x, const float* scale, int64_t R, int64_t K, uint16_t* sp, hipStream_t st) {
   int64_t blocks = (R * split_kp(K) + 255) / 256;
   const int64_t cap = (int64_t)num_cus() * 16;
@@ -352,83 +342,39 @@ inline int launch_split(const float* x, const float* scale, int64_t R, int64_t K
   return 0;
 }
 
-// ---- column-strip split (round 5) --------------------------------------------------------------------------------------------
-// The 256 x 256 kernel runs whole rounds of tiles; a trailing partial column tile (N = 1152 = 4.5 tiles: SigLIP-so400m's o-proj and
-// fc2) costs a whole extra column of tiles, and with 64 row tiles (a 64-image call) 320 tiles are 1.25 rounds that take 1.77.  When
-// the model below says so, the GEMM is cut at the last full column tile: columns [0, 256 n) keep the big kernel (256 tiles = ONE
-// round) and the remainder strip — the same A, B rows from 256 n on, the epilogue shifted by 256 n columns — goes to whatever the
-// grid-size rules pick for a strip that narrow (128 x 128 tiles).  Every output element keeps its accumulation order (all tile
-// variants are bit-identical), so results do not change.  Measured (`tools/gemm_strip_lab.py`, profiles/r05_gemm_strip_lab.txt):
-// M = 16 384: o-proj 173 -> 98 + 31 us, fc2 514 -> 310 + 96 us; M = 65 536: 495 -> 384 + 80, 1 523 -> 1 194 + 257.
-// The cut may also fall one or two FULL tiles earlier when that lands the big kernel on whole rounds.
-// Cost model, in rounds of the big kernel: t tiles cost floor(t / CUs) + (0.7 + 0.3 f) for a partial round filling a fraction f of
-// the CUs; a strip of s 128 x 128 tiles costs 0.12 + 0.0014 s.  Option g3_strip_off = 1 switches the split off.
-inline double g8_rounds_model(int64_t tiles, int64_t cus) {
-  const int64_t full = tiles / cus, rem = tiles % cus;
-  return (double)full + (rem ? 0.7 + 0.3 * (double)rem / (double)cus : 0.0);
-}
-inline int64_t strip_split_columns(int64_t M, int64_t N) {
-  const bool on = option(OPT_G3_STRIP_OFF) == 0;
-  const int64_t cus = num_cus();
-  const int64_t tm = (M + 255) / 256, tn = (N + 255) / 256;
-  if (!on || tn < 2) return 0;
-  const double whole = g8_rounds_model(tm * tn, cus);
-  // cut after m full column tiles, the strip up to three tiles wide: so400m's QKV at 64 images (N = 3456 = 13.5 tiles, 896 tiles =
-  // 3.5 rounds) runs 12 column tiles in exactly three rounds and a 384-column strip
-  int64_t best_m = 0;
-  double best = 0.97 * whole;
-  for (int64_t m = tn - 1; m >= 1 && m >= tn - 3; --m) {
-    const int64_t rest = N - m * 256;
-    const int64_t strip_tiles = ((M + 127) / 128) * ((rest + 127) / 128);
-    const double cut = g8_rounds_model(tm * m, cus) + 0.12 + 0.0014 * (double)strip_tiles;
-    if (cut < best) best = cut, best_m = m;
-  }
-  return best_m * 256;
-}
+// ---- launcher ---------------------------------------------------------------------------------------------------------------
+using gemm_choice::G3Kernel;
+using gemm_choice::G3Part;
 
-// A (M rows), B (N rows): split matrices of K columns (layout above)
+// A (M rows), B (N rows): split matrices of K columns (layout above).  The kernel is gemm_choice.hpp's rule on this device and the
+// options of this dispatch: "g3_tile" (sl_set_option; tests) forces a kernel, "g3_strip_off" = 1 switches the column-strip cut off.
 template <class Epi>
 int launch_gemm3_nt(ProfScope& prof, const uint16_t* A, int64_t M, const uint16_t* B, int64_t N, int64_t K, const Epi& epi,
-                    hipStream_t st, int may_split = 1) {  // 1: may cut a strip off, 0: the main part of a cut, 2: the strip itself
+                    hipStream_t st, G3Part part = G3Part::Whole) {
   const int64_t tm = (M + BM - 1) / BM, tn = (N + BN - 1) / BN;
   SL_REQUIRE(tm * tn < (1ll << 31), "GEMM: too many tiles");
   if (tm * tn == 0) return 0;
   const int64_t Kp = split_kp(K);
-  // option "g3_tile" (sl_set_option; tests): 128: register-staged 128 x 128 tiles, 256: LDS-DMA staged 256 x 128 tiles, 8: 8-phase
-  // 256 x 256, 160: 160 x 256 four-wave three-slot (gemm_w4.hpp), 64 / 1280: 64 x 64 eight-slot / 128 x 128 four-slot ring for small
-  // grids (gemm_skinny.hpp); 0: by grid size
-  const int forced = (int)option(OPT_G3_TILE);
-  if (may_split == 2 && !forced && gemm8::fits(M, N, 4 * Kp) && Kp / 32 >= 8 && !gemmsk::prefer(M, N, Kp / 32))
-    return gemmsk::launch<2>(prof, A, M, B, N, 4 * Kp, Kp / 32, epi, st);  // strips are priced (and run) as 128 x 128 tiles
-  if (may_split == 1 && !forced && gemm8::fits(M, N, 4 * Kp) && gemm8::worth_it(M, N) && !gemmw4::prefer(M, N) &&
-      !gemmsk::prefer(M, N, Kp / 32)) {
-    const int64_t c0 = strip_split_columns(M, N);
-    if (c0 > 0) {
-      if (int rc = launch_gemm3_nt(prof, A, M, B, c0, K, epi, st, 0)) return rc;
-      ProfScope strip(SL_PROF_GEMM, st, 0.0);  // its time counts, its flops are in `prof`'s work already
-      return launch_gemm3_nt(strip, A, M, B + c0 * 2 * Kp, N - c0, K, epi.shifted(c0), st, 2);
-    }
+  const bool strip_off = option(OPT_G3_STRIP_OFF) != 0;
+  const auto c = gemm_choice::choose_g3(M, N, Kp, num_cus(), (int)option(OPT_G3_TILE), strip_off, part);
+  if (c.cut > 0) {  // columns [0, cut), then the strip: the same A, B rows from `cut` on, the epilogue shifted by `cut` columns
+    if (int rc = launch_gemm3_nt(prof, A, M, B, c.cut, K, epi, st, G3Part::Main)) return rc;
+    ProfScope strip(SL_PROF_GEMM, st, 0.0);  // its time counts, its flops are in `prof`'s work already
+    return launch_gemm3_nt(strip, A, M, B + c.cut * 2 * Kp, N - c.cut, K, epi.shifted(c.cut), st, G3Part::Strip);
   }
-  const int64_t tm3 = (M + BM3 - 1) / BM3;
-  // gemm_skinny.hpp: 64 x 64 tiles behind an eight-stage LDS-DMA ring for small grids with long k loops
-  if (gemm8::fits(M, N, 4 * Kp) && (forced ? forced == 64 : gemmsk::prefer(M, N, Kp / 32)))
-    return gemmsk::launch<1>(prof, A, M, B, N, 4 * Kp, Kp / 32, epi, st);
-  if (forced == 1280 && gemm8::fits(M, N, 4 * Kp)) return gemmsk::launch<2>(prof, A, M, B, N, 4 * Kp, Kp / 32, epi, st);
-  // gemm_w4.hpp: 160 x 256 tiles where they shorten the makespan (150-tile GEMMs of the encoder: 240 items in one round)
-  if (gemm8::fits(M, N, 4 * Kp) && (forced ? forced == 160 : gemmw4::prefer(M, N)))
-    return gemmw4::launch<5>(prof, A, M, B, N, 4 * Kp, Kp / 32, epi, st);
-  const bool k4 = gemm8::fits(M, N, 4 * Kp) && (forced ? forced == 8 : gemm8::worth_it(M, N));
-  const bool k2 = forced ? forced == 256 : tm3 * tn >= (int64_t)8 * num_cus();
-  if (k4)  // gemm_8phase.hpp; a row of a split matrix is 2 Kp bf16 = 4 Kp bytes, one 128-byte line per k-tile
-    return gemm8::launch<gemm8::MODE_BF16X3>(prof, A, M, B, N, 4 * Kp, Kp / 32, epi, st);
-  else if (k2)
-    SL_LAUNCH(prof, (gemm3_nt_dma256_kernel<Epi>), dim3((unsigned)(tm3 * tn)), dim3(256), 0, st, A, B, M, N, Kp, (int)tn, epi);
-  else if (!forced && gemm8::fits(M, N, 4 * Kp) && Kp / 32 >= 8)
-    // mid-size grids: the same 128 x 128 tiles behind the four-stage LDS-DMA ring of gemm_skinny.hpp (5-30 % under the
-    // register-staged kernel from 450 to 2 400 tiles, equal at 4 800; tools/enc_gemm_lab.py <M> with SL_G3_TILE = 128 / 1280)
-    return gemmsk::launch<2>(prof, A, M, B, N, 4 * Kp, Kp / 32, epi, st);
-  else
-    SL_LAUNCH(prof, (gemm3_nt_kernel<Epi>), dim3((unsigned)(tm * tn)), dim3(256), 0, st, A, B, M, N, Kp, (int)tn, epi);
+  switch (c.kernel) {  // the ring kernels take byte rows: 2 Kp bf16 = 4 Kp bytes, one 128-byte line per k-tile
+    case G3Kernel::Ring64: return gemmsk::launch<1>(prof, A, M, B, N, 4 * Kp, Kp / 32, epi, st);
+    case G3Kernel::Ring128: return gemmsk::launch<2>(prof, A, M, B, N, 4 * Kp, Kp / 32, epi, st);
+    case G3Kernel::W4: return gemmw4::launch<5>(prof, A, M, B, N, 4 * Kp, Kp / 32, epi, st);
+    case G3Kernel::Phase8: return gemm8::launch<gemm8::MODE_BF16X3>(prof, A, M, B, N, 4 * Kp, Kp / 32, epi, st);
+    case G3Kernel::Dma256:
+      SL_LAUNCH(prof, (gemm3_nt_dma256_kernel<Epi>), dim3((unsigned)((M + BM3 - 1) / BM3 * tn)), dim3(256), 0, st, A, B, M, N, Kp,
+                (int)tn, epi);
+      break;
+    case G3Kernel::Reg128:
+      SL_LAUNCH(prof, (gemm3_nt_kernel<Epi>), dim3((unsigned)(tm * tn)), dim3(256), 0, st, A, B, M, N, Kp, (int)tn, epi);
+      break;
+  }
   SL_CHECK_HIP(hipGetLastError());
   return 0;
 }

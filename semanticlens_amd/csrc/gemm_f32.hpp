@@ -10,15 +10,12 @@
 // The K tail is peeled out of the steady-state loop; rows past the matrix edge are clamped onto the last row
 // (their products land in outputs the epilogue never stores).
 #pragma once
-#include <cstdlib>
-
-#include "common.hpp"
+#include "gemm_ring.hpp"
 #include "gemm_8phase.hpp"
 
 namespace sl {
 namespace gemm {
 
-typedef float floatx16 __attribute__((ext_vector_type(16)));
 constexpr int BM = 128, BN = 128, BK = 32, LDS_LD = BK + 4;
 
 template <bool VEC>
@@ -189,16 +186,17 @@ int launch_gemm_nt(ProfScope& prof, const float* A, int64_t M, const float* B, i
   const int64_t tm = (M + BM - 1) / BM, tn = (N + BN - 1) / BN;
   SL_REQUIRE(tm * tn < (1ll << 31), "GEMM: too many tiles");
   if (tm * tn == 0) return 0;
-  const bool vec = (K % 4 == 0) && (((uintptr_t)A | (uintptr_t)B) & 15) == 0;
-  // Large grids whose rows are whole 128-byte lines: the 256 x 256 8-phase kernel (gemm_8phase.hpp), same bits.
-  // option "f32_tile" = 128 / 8 forces one of the two (tests).
-  const int forced = (int)option(OPT_F32_TILE);
-  if (vec && K % 32 == 0 && K > 0 && gemm8::fits(M, N, K * 4) && (forced ? forced == 8 : gemm8::worth_it_f32(M, N)))
-    return gemm8::launch<gemm8::MODE_F32>(prof, A, M, B, N, K * 4, K / 32, epi, st);
-  if (vec)
-    SL_LAUNCH(prof, (gemm_nt_kernel<true, Epi>), dim3((unsigned)(tm * tn)), dim3(256), 0, st, A, B, M, N, K, (int)tn, epi);
-  else
-    SL_LAUNCH(prof, (gemm_nt_kernel<false, Epi>), dim3((unsigned)(tm * tn)), dim3(256), 0, st, A, B, M, N, K, (int)tn, epi);
+  // gemm_choice.hpp's rule on this device; option "f32_tile" = 128 / 8 forces one of the two tile sizes (tests).  Same bits.
+  const bool aligned16 = (((uintptr_t)A | (uintptr_t)B) & 15) == 0;
+  switch (gemm_choice::choose_f32(M, N, K, aligned16, num_cus(), (int)option(OPT_F32_TILE))) {
+    case gemm_choice::F32Kernel::Phase8: return gemm8::launch<gemm8::MODE_F32>(prof, A, M, B, N, K * 4, K / 32, epi, st);
+    case gemm_choice::F32Kernel::Vec128:
+      SL_LAUNCH(prof, (gemm_nt_kernel<true, Epi>), dim3((unsigned)(tm * tn)), dim3(256), 0, st, A, B, M, N, K, (int)tn, epi);
+      break;
+    case gemm_choice::F32Kernel::Scalar128:
+      SL_LAUNCH(prof, (gemm_nt_kernel<false, Epi>), dim3((unsigned)(tm * tn)), dim3(256), 0, st, A, B, M, N, K, (int)tn, epi);
+      break;
+  }
   SL_CHECK_HIP(hipGetLastError());
   return 0;
 }

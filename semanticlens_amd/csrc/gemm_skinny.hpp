@@ -16,15 +16,10 @@
 // 16-wide k-step) as every kernel of gemm_bf16x3.hpp: bit-identical results, so an embedding does not depend on the batch it
 // was computed in (tests/test_gpu_parity.py::test_gemm_tile_variants_are_bit_identical, test_gpu_native_clip.py).
 #pragma once
-#include "common.hpp"
-#include "gemm_epilogue.hpp"
+#include "gemm_ring.hpp"
 
 namespace sl {
 namespace gemmsk {
-
-typedef float floatx16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 // WT = accumulator tiles per wave and side: 1 -> 64 x 64 tiles, eight 16-KB slots; 2 -> 128 x 128 tiles (each wave 64 x 64),
 // four 32-KB slots, for the mid-size grids above (the same ring in front of four times the MFMAs per step)
@@ -53,7 +48,7 @@ __global__ __launch_bounds__(256, 1) void gemm3_nt_skinny_kernel(const unsigned 
   const int64_t m0 = (int64_t)(blockIdx.x / tiles_n) * BM;
   const int64_t n0 = (int64_t)(blockIdx.x % tiles_n) * BN;
 
-  floatx16 acc[WT][WT];
+  floatx16 acc[WT][WT];  // spelled out: `= {}`, as the other ring kernels zero theirs, changes this kernel's instruction stream
 #pragma unroll
   for (int t = 0; t < WT; ++t)
 #pragma unroll
@@ -69,25 +64,23 @@ __global__ __launch_bounds__(256, 1) void gemm3_nt_skinny_kernel(const unsigned 
     const bool isa = g < BM / 8;
     const int row0 = isa ? g * 8 : (g - BM / 8) * 8;
     const int row = row0 + (lane >> 3);
-    const int chunk = (lane & 7) ^ ((row >> 1) & 7);
-    if (isa) src[i] = (uint32_t)((m0 + row < M ? m0 + row : M - 1) * row_bytes + chunk * 16);
-    else src[i] = (uint32_t)((n0 + row < N ? n0 + row : N - 1) * row_bytes + chunk * 16);
+    const int chunk = ring::dma_chunk(lane, row);
+    if (isa) src[i] = ring::dma_src(m0, row, M, row_bytes, chunk);
+    else src[i] = ring::dma_src(n0, row, N, row_bytes, chunk);
   }
-  typedef __attribute__((address_space(3))) void lds_void;
-  typedef const __attribute__((address_space(1))) void glb_void;
   auto issue = [&](int stage) __attribute__((always_inline)) {
     unsigned char* slot = smem + (stage & (NSLOT - 1)) * STAGE_BYTES;
 #pragma unroll
     for (int i = 0; i < NI; ++i) {
       const bool isa = w + 4 * i < BM / 8;  // wave-uniform
       const unsigned char* base = (isa ? A : B) + (int64_t)stage * 128;
-      __builtin_amdgcn_global_load_lds((glb_void*)(base + src[i]), (lds_void*)(slot + (w + 4 * i) * 1024), 16, 0, 0);
+      ring::dma16(base + src[i], slot + (w + 4 * i) * 1024);
     }
   };
   // fragment addresses inside a stage slot (k-half 0, hi halves; k-half -> ^32, lo -> ^64)
   // (accumulator tile t / j of the wave: + 4096 t / + 4096 j — 32 lines; the swizzle repeats every 16 lines)
-  const int a_addr = (wm * 32 * WT + li) * 128 + ((lh ^ ((li >> 1) & 7)) << 4);
-  const int b_addr = A_BYTES + (wn * 32 * WT + li) * 128 + ((lh ^ ((li >> 1) & 7)) << 4);
+  const int a_addr = (wm * 32 * WT + li) * 128 + ((lh ^ ring::swz(li)) << 4);
+  const int b_addr = A_BYTES + (wn * 32 * WT + li) * 128 + ((lh ^ ring::swz(li)) << 4);
 
   auto wait_landed = [&](int ahead) __attribute__((always_inline)) {  // at most `ahead` younger stages still in flight
     switch (ahead) {
@@ -98,9 +91,7 @@ __global__ __launch_bounds__(256, 1) void gemm3_nt_skinny_kernel(const unsigned 
     }
   };
   auto step = [&](int s, bool fetch) __attribute__((always_inline)) {
-    __builtin_amdgcn_sched_barrier(0);
-    __builtin_amdgcn_s_barrier();  // stage s is visible to everyone; everyone is done with the slot of stage s - 1
-    __builtin_amdgcn_sched_barrier(0);
+    ring::raw_barrier();  // stage s is visible to everyone; everyone is done with the slot of stage s - 1
     const unsigned char* buf = smem + (s & (NSLOT - 1)) * STAGE_BYTES;
     u32x4 fa[2][WT][2], fb[2][WT][2];  // [k-half][tile][hi, lo]
 #pragma unroll
@@ -156,26 +147,10 @@ __global__ __launch_bounds__(256, 1) void gemm3_nt_skinny_kernel(const unsigned 
 template <int WT, class Epi>
 int launch(ProfScope& prof, const void* A, int64_t M, const void* B, int64_t N, int64_t row_bytes, int64_t ns, const Epi& epi,
            hipStream_t st) {
-  constexpr int BM = Cfg<WT>::BM, BN = Cfg<WT>::BN;
-  const int64_t tm = (M + BM - 1) / BM, tn = (N + BN - 1) / BN;
-  SL_REQUIRE(tm * tn < (1ll << 31) && ns < (1ll << 29), "GEMM: too many tiles");
-  SL_REQUIRE((M > N ? M : N) * row_bytes < (1ll << 32), "GEMM: operand larger than 4 GB (use another kernel)");
-  if (tm * tn == 0) return 0;
-  SL_LAUNCH(prof, (gemm3_nt_skinny_kernel<WT, Epi>), dim3((unsigned)(tm * tn)), dim3(256), 0, st, (const unsigned char*)A,
-            (const unsigned char*)B, M, N, row_bytes, (int)ns, (int)tn, epi);
-  SL_CHECK_HIP(hipGetLastError());
-  return 0;
-}
-
-// Up to two 64 x 64 tiles per CU, k loops long enough for the ring to matter; beyond that the 128 x 128 instance (the caller's
-// fallback for mid-size grids) is as fast or faster.  Measured on the ViT-B/32 block shapes (tools/enc_gemm_lab.py <M>,
-// SL_G3_TILE = 64 / 1280 / 128 = this kernel / its 128 x 128 instance / the register-staged 128 x 128 kernel), us:
-//   M =   256: o-proj  8 /  - / 30, fc2 22 /  - / 90, qkv  9 /  - / 30, fc1  9 /  - / 35
-//   M = 1 600: o-proj 19 / 29 / 32, fc2 48 / 68 / 89 (300 tiles); qkv 34 / 29 / 33 (900), fc1 47 / 50 / 53 (1 200)
-//   M = 3 200: o-proj 28 / 24 / 36, fc2 74 / 67 / 95 (600 tiles); qkv 67 / 45 / 50, fc1 88 / 69 / 73
-inline bool prefer(int64_t M, int64_t N, int64_t ns) {
-  const int64_t t64 = ((M + 63) / 64) * ((N + 63) / 64);
-  return t64 <= 2 * (int64_t)num_cus() && ns >= 8;
+  return ring::launch_tiles(M, N, Cfg<WT>::BM, Cfg<WT>::BN, row_bytes, ns, [&](int64_t tm, int64_t tn) {
+    SL_LAUNCH(prof, (gemm3_nt_skinny_kernel<WT, Epi>), dim3((unsigned)(tm * tn)), dim3(256), 0, st, (const unsigned char*)A,
+              (const unsigned char*)B, M, N, row_bytes, (int)ns, (int)tn, epi);
+  });
 }
 
 }  // namespace gemmsk

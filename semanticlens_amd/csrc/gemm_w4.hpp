@@ -17,36 +17,17 @@
 // Same operands, LDS image, swizzle and per-element accumulation order as every kernel of gemm_bf16x3.hpp: bit-identical
 // results (tests/test_gpu_parity.py::test_gemm_tile_variants_are_bit_identical).
 #pragma once
-#include "common.hpp"
-#include "gemm_epilogue.hpp"
+#include "gemm_ring.hpp"
 
 namespace sl {
 namespace gemmw4 {
 
-typedef float floatx16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+using ring::IntC;
+using ring::raw_barrier;
+using ring::static_for;
 
 constexpr int BN = 256;
 constexpr int NSLOT = 3;
-#ifndef SL_GW4_RD
-#define SL_GW4_RD 0  // lab: 1 = all reads of a half in one burst behind its first MFMA, 2 = in pairs behind every second
-#endif
-#ifndef SL_GW4_EXP
-#define SL_GW4_EXP 0  // lab only (garbage results): 1 = no LDS-DMA in the k loop, 2 = no fragment reads, 3 = neither, 4 = no epilogue
-#endif
-
-template <int N_>
-struct IntC {
-  static constexpr int value = N_;
-};
-template <int I, int N_, class F>
-__device__ __forceinline__ void static_for(F&& f) {
-  if constexpr (I < N_) {
-    f(IntC<I>());
-    static_for<I + 1, N_>(f);
-  }
-}
 
 template <int TM>
 struct Cfg {
@@ -73,56 +54,36 @@ __global__ __launch_bounds__(256, 1) void gemm3_nt_w4_kernel(const unsigned char
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);  // 0..3: columns 64 w ..
   const int li = lane & 31, lh = lane >> 5;
   int tm_i, tn_i;
-  {  // XCD-aware tile order, as in gemm_8phase.hpp
-    const int nwg = tiles_m * tiles_n;
-    const int xcd = blockIdx.x & 7, idx = blockIdx.x >> 3;
-    const int q = nwg >> 3, r = nwg & 7;
-    const int tile = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-    constexpr int GROUP_M = 4;
-    const int band = tile / (GROUP_M * tiles_n);
-    const int first_m = band * GROUP_M;
-    const int rows = tiles_m - first_m < GROUP_M ? tiles_m - first_m : GROUP_M;
-    const int in_band = tile - band * GROUP_M * tiles_n;
-    tm_i = first_m + in_band % rows;
-    tn_i = in_band / rows;
-  }
+  ring::xcd_tile(tiles_m, tiles_n, tm_i, tn_i);
   const int64_t m0 = (int64_t)tm_i * C::BM;
   const int64_t n0 = (int64_t)tn_i * BN;
 
-  floatx16 acc[TM][2];
-#pragma unroll
-  for (int t = 0; t < TM; ++t)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[t][j][e] = 0.f;
+  floatx16 acc[TM][2] = {};
 
   // ---- LDS-DMA plan: row group g = w + 4 i of the stage: groups 0 .. 4 TM - 1 are A rows 8 g .., the rest B rows
-  uint32_t src[C::NI];  // byte offset of this lane's 16 bytes in k-tile 0 (operands < 4 GB)
+  uint32_t src[C::NI];  // ring::dma_src of the group's row lane >> 3
 #pragma unroll
   for (int i = 0; i < C::NI; ++i) {
     const int g = w + 4 * i;
     const bool isa = g < 4 * TM;
     const int row0 = isa ? g * 8 : (g - 4 * TM) * 8;
     const int row = row0 + (lane >> 3);
-    const int chunk = (lane & 7) ^ ((row >> 1) & 7);
-    if (isa) src[i] = (uint32_t)((m0 + row < M ? m0 + row : M - 1) * row_bytes + chunk * 16);
-    else src[i] = (uint32_t)((n0 + row < N ? n0 + row : N - 1) * row_bytes + chunk * 16);
+    const int chunk = ring::dma_chunk(lane, row);
+    if (isa) src[i] = ring::dma_src(m0, row, M, row_bytes, chunk);
+    else src[i] = ring::dma_src(n0, row, N, row_bytes, chunk);
   }
-  typedef __attribute__((address_space(3))) void lds_void;
-  typedef const __attribute__((address_space(1))) void glb_void;
   auto issue = [&](int stage, int slot_off, auto Ic) __attribute__((always_inline)) {
     constexpr int i = decltype(Ic)::value;
     const bool isa = w + 4 * i < 4 * TM;  // wave-uniform
     const unsigned char* base = (isa ? A : B) + (int64_t)stage * 128;
     unsigned char* l = smem + slot_off + (w + 4 * i) * 1024;  // A rows then B rows: row group g sits at g KiB of the slot
-    __builtin_amdgcn_global_load_lds((glb_void*)(base + src[i]), (lds_void*)l, 16, 0, 0);
+    ring::dma16(base + src[i], l);
   };
 
   // ---- fragment addresses inside a stage slot (k-half 0, hi halves; the others are XORs: k-half -> ^32, lo -> ^64)
   int a_addr, b_addr;  // tile t / column tile j: + 4096 t / + 4096 j (32 lines; the swizzle repeats every 16 lines)
-  a_addr = li * 128 + ((lh ^ ((li >> 1) & 7)) << 4);
-  b_addr = C::A_BYTES + (w * 64 + li) * 128 + ((lh ^ ((li >> 1) & 7)) << 4);
+  a_addr = li * 128 + ((lh ^ ring::swz(li)) << 4);
+  b_addr = C::A_BYTES + (w * 64 + li) * 128 + ((lh ^ ring::swz(li)) << 4);
   u32x4 fa[2][TM][2], fb[2][2][2];  // [set][tile][hi, lo]
 
   // read r of the NR fragment reads of k-half `kh` of the slot at `buf` into set `set`
@@ -135,11 +96,6 @@ __global__ __launch_bounds__(256, 1) void gemm3_nt_w4_kernel(const unsigned char
       constexpr int j = (r - 2 * TM) >> 1, lo = r & 1;
       fb[set][j][lo] = *reinterpret_cast<const u32x4*>(buf + ((b_addr ^ (kh * 32) ^ (lo * 64)) + j * 4096));
     }
-  };
-  auto raw_barrier = [&]() __attribute__((always_inline)) {
-    __builtin_amdgcn_sched_barrier(0);
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_sched_barrier(0);
   };
 
   // One half: 6 TM MFMAs of k-half KH of the stage in slot `cur` from fragment set KH; behind MFMA i < NR, read i of the next
@@ -158,32 +114,15 @@ __global__ __launch_bounds__(256, 1) void gemm3_nt_w4_kernel(const unsigned char
       acc[t][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, fa[KH][t][alo]),
                                                           __builtin_bit_cast(bf16x8, fb[KH][j][blo]), acc[t][j], 0, 0, 0);
       __builtin_amdgcn_sched_barrier(0);
-#if SL_GW4_RD == 1
-      if constexpr (i == 0) {
-        if (!(SL_GW4_EXP & 2))
-          static_for<0, C::NR>([&](auto Rc) __attribute__((always_inline)) { read_frag(rbuf, IntC<1 - KH>(), IntC<1 - KH>(), Rc); });
-      }
       if constexpr (i < C::NR) {
+        read_frag(rbuf, IntC<1 - KH>(), IntC<1 - KH>(), Ic);
       } else {
-#elif SL_GW4_RD == 2
-      if constexpr (i < C::NR) {
-        if constexpr (i % 2 == 0 && i / 2 < C::NR)
-          if (!(SL_GW4_EXP & 2)) {
-            read_frag(rbuf, IntC<1 - KH>(), IntC<1 - KH>(), IntC<i>());
-            read_frag(rbuf, IntC<1 - KH>(), IntC<1 - KH>(), IntC<i + 1>());
-          }
-      } else {
-#else
-      if constexpr (i < C::NR) {
-        if (!(SL_GW4_EXP & 2)) read_frag(rbuf, IntC<1 - KH>(), IntC<1 - KH>(), Ic);
-      } else {
-#endif
         // LDS-DMA issue d of this half sits behind MFMA NR + d (NM - NR) / ND
         constexpr int span = C::NM - C::NR;
         static_for<0, ND>([&](auto Dc) __attribute__((always_inline)) {
           constexpr int d = decltype(Dc)::value;
           if constexpr (i == C::NR + d * span / ND) {
-            if (do_fetch && !(SL_GW4_EXP & 1)) issue(fetch_stage, fetch_off, IntC<D0 + d>());
+            if (do_fetch) issue(fetch_stage, fetch_off, IntC<D0 + d>());
           }
         });
       }
@@ -237,17 +176,6 @@ __global__ __launch_bounds__(256, 1) void gemm3_nt_w4_kernel(const unsigned char
     for (; s < ns; ++s) stage_body(s, IntC<1>());
   }
 
-  if (SL_GW4_EXP & 4) {  // lab: no epilogue (one impossible store keeps the accumulators alive)
-    float t = 0.f;
-#pragma unroll
-    for (int tt = 0; tt < TM; ++tt)
-#pragma unroll
-      for (int j = 0; j < 2; ++j)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) t += acc[tt][j][e];
-    if (t == 12345.678f) epi.store(m0, n0, t, epi.column(n0));
-    return;
-  }
   if (m0 + C::BM <= M && n0 + BN <= N) {
 #pragma unroll
     for (int t = 0; t < TM; ++t)
@@ -266,27 +194,10 @@ __global__ __launch_bounds__(256, 1) void gemm3_nt_w4_kernel(const unsigned char
 template <int TM, class Epi>
 int launch(ProfScope& prof, const void* A, int64_t M, const void* B, int64_t N, int64_t row_bytes, int64_t ns, const Epi& epi,
            hipStream_t st) {
-  typedef Cfg<TM> C;
-  const int64_t tm = (M + C::BM - 1) / C::BM, tn = (N + BN - 1) / BN;
-  SL_REQUIRE(tm * tn < (1ll << 31) && ns < (1ll << 29), "GEMM: too many tiles");
-  SL_REQUIRE((M > N ? M : N) * row_bytes < (1ll << 32), "GEMM: operand larger than 4 GB (use another kernel)");
-  if (tm * tn == 0) return 0;
-  SL_LAUNCH(prof, (gemm3_nt_w4_kernel<TM, Epi>), dim3((unsigned)(tm * tn)), dim3(256), 0, st, (const unsigned char*)A,
-            (const unsigned char*)B, M, N, row_bytes, (int)ns, (int)tm, (int)tn, epi);
-  SL_CHECK_HIP(hipGetLastError());
-  return 0;
-}
-
-// 160-row tiles when they shorten the makespan: rounds x tile time.  A 160 x 256 tile does 0.625 of the work of a 256 x 256
-// one and measures 0.80 (K = 768) to 0.87 (K = 3072) of its time (tools/enc_gemm_lab.py, bare epilogue: o-proj 51 -> 41 us,
-// fc2 147 -> 128 us), so it is chosen only where a whole round is saved.
-inline bool prefer(int64_t M, int64_t N) {
-  const int64_t cus = num_cus();
-  const int64_t t256 = ((M + 255) / 256) * ((N + 255) / 256), t160 = ((M + 159) / 160) * ((N + 255) / 256);
-  if (t256 * 2 < cus) return false;  // small grids stay on the 128 x 128 kernel's side of the choice
-  const double c256 = (double)((t256 + cus - 1) / cus);
-  const double c160 = (double)((t160 + cus - 1) / cus) * 0.88;
-  return c160 < c256 * 0.97;
+  return ring::launch_tiles(M, N, Cfg<TM>::BM, BN, row_bytes, ns, [&](int64_t tm, int64_t tn) {
+    SL_LAUNCH(prof, (gemm3_nt_w4_kernel<TM, Epi>), dim3((unsigned)(tm * tn)), dim3(256), 0, st, (const unsigned char*)A,
+              (const unsigned char*)B, M, N, row_bytes, (int)ns, (int)tm, (int)tn, epi);
+  });
 }
 
 }  // namespace gemmw4

@@ -1124,10 +1124,10 @@ def test_fused_multi_layer_probe_equals_per_layer_similarity():
 
 
 def test_gemm_tile_variants_are_bit_identical(tmp_path):
-    """The 128x128 register-staged, the 256x128 LDS-DMA staged, the 256x256 ping-pong, the 256x256 8-phase, the 160x256
-    four-wave and the 64x64 / 128x128 ring (round 3: "160", "64", "1280") split-bf16 kernels accumulate every output element in
-    the same order: same bits (the variant is
-    latched per process, hence subprocesses).  Forcing a variant sends EVERY shape through it, ragged and tiny ones included."""
+    """The 128x128 register-staged, the 256x128 LDS-DMA staged, the 256x256 8-phase, the 160x256 four-wave and the 64x64 /
+    128x128 ring (round 3: "160", "64", "1280") split-bf16 kernels accumulate every output element in the same order: same bits.
+    Options are read on every dispatch, not latched; each variant still gets a process of its own here, preset through SL_OPTIONS.
+    Forcing a variant sends EVERY shape through it, ragged and tiny ones included."""
     import os
     import subprocess
     import sys
@@ -1167,6 +1167,34 @@ torch.save(outs, sys.argv[1])
         f32[tile] = torch.load(out)
     for a, b in zip(f32["128"], f32["8"]):
         assert torch.equal(a, b), ("f32", tuple(a.shape))
+
+
+def test_every_arm_of_the_gemm_launch_switch_gives_the_register_staged_kernels_bits():
+    """The smallest shapes that reach each arm of the launch `switch` of launch_gemm3_nt / launch_gemm_nt at 256 CUs — 64 x 64 and
+    128 x 128 ring, register-staged (7 k-tiles), 160 x 256, 8-phase, a column cut (8-phase + strip), and the fp32 mode's 8-phase /
+    vectorised / scalar kernels — by the dispatcher's own rule (tile option 0) against the 128 x 128 register-staged kernel forced:
+    same bits.  Which kernel a shape gets is tests/native/gemm_choice_check.cpp's subject, not this test's.  (161, 257, 20) has
+    K < 64, where `similarity` takes the fp32 GEMM in either mode.)  In-process: options are read per dispatch."""
+    g3_shapes = [(130, 257, 256), (1, 5, 4096), (2304, 1024, 256), (2304, 1024, 200), (161, 257, 20), (12800, 768, 256),
+                 (8192, 2048, 256), (10000, 9216, 1152), (16384, 1152, 256), (300, 301, 104)]
+    f32_shapes = [(8192, 2048, 256), (130, 257, 72), (129, 128, 73)]
+    torch.manual_seed(11)
+    try:
+        for mode, option, shapes in (("bf16x3", "g3_tile", g3_shapes), ("f32", "f32_tile", f32_shapes)):
+            N.set_gemm_mode(mode)
+            for (m, n, k) in shapes:
+                x, y = torch.randn(m, k, device=DEV), torch.randn(n, k, device=DEV)
+                N.set_option(option, 0)
+                by_rule = N.similarity(x, y)
+                N.set_option(option, 128)
+                forced = N.similarity(x, y)
+                N.set_option(option, 0)
+                assert by_rule.shape == (m, n)
+                assert torch.equal(by_rule, forced), (mode, m, n, k)
+    finally:
+        N.set_option("g3_tile", 0)
+        N.set_option("f32_tile", 0)
+        N.set_gemm_mode(None)
 
 
 def test_linear_epilogues_are_bit_identical_across_tile_variants_on_ragged_shapes(tmp_path):
@@ -1212,7 +1240,7 @@ torch.save(outs, sys.argv[1])
 
 
 def test_column_strip_split_keeps_every_bit(tmp_path):
-    """A GEMM whose last column tile is partial may be cut at the last full tile (gemm_bf16x3.hpp `strip_split_columns`: the big
+    """A GEMM whose last column tile is partial may be cut at the last full tile (gemm_choice.hpp `strip_split_columns`: the big
     kernel on the first 256 n columns, the strip's own kernel on the rest with the epilogue shifted): same bits as the uncut GEMM
     (option `g3_strip_off`) for every epilogue — plain, cosine routing over several layers, bias, residual in place, GELU -> split output,
     scattered rows + positional table — at shapes the cost model does cut (so400m's N = 1152 and 4304 at 64 images, 3 x 257 layers)."""

@@ -877,6 +877,17 @@ def test_reduce_policy_header_on_the_host(tmp_path):
     assert "failures=0" in res.stdout
 
 
+def test_gemm_choice_header_on_the_host(tmp_path):
+    """csrc/gemm_choice.hpp compiled for the host: which kernel, and which column cut, `choose_g3` / `choose_f32` pick per shape,
+    CU count and forced option (tests/native/gemm_choice_check.cpp holds the table, recorded from the launchers' former if-chains)."""
+    exe = tmp_path / "gemm_choice_check"
+    subprocess.run(["g++", "-O2", "-std=c++17", "-Wall", "-Wextra", "-o", str(exe),
+                    str(ROOT / "tests" / "native" / "gemm_choice_check.cpp")], check=True)
+    res = subprocess.run([str(exe)], capture_output=True, text=True)
+    assert res.returncode == 0, res.stdout + res.stderr
+    assert "failures=0" in res.stdout
+
+
 # ---- the aten tie order's host self-test (VERDICT r05 #12): restatement vs the installed torch.topk, no device -----------------------
 def test_aten_order_restatement_equals_the_installed_torch_topk():
     """`sl_aten_topk_order_host` is host code: the positions the K3 kernels' restatement selects against `torch.topk` on the CPU of

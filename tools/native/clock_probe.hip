@@ -20,6 +20,7 @@ struct ProbeEpi {
   float* out; int64_t ldc; unsigned long long* probe;
   __device__ float column(int64_t) const { return 0.f; }
   __device__ void store(int64_t r, int64_t c, float acc, float) const { out[r * ldc + c] = acc; }
+  ProbeEpi shifted(int64_t c0) const { return ProbeEpi{out + c0, ldc, probe}; }  // column-strip split of launch_gemm3_nt
 };
 
 
