@@ -483,6 +483,21 @@ size_t sl_topk_merge_ws_bytes(int64_t R, int64_t k, int64_t B);
 int sl_topk_merge_states(float* d_vals, int64_t* d_ids, int64_t R, int64_t k, const float* d_other_vals,
                          const int64_t* d_other_ids, int64_t M, void* stream);
 
+/* ---- K20: mutual best matches out of one cosine tile — the selection behind compare_concept_dbs -------
+ * No reference counterpart.  Two states of one uint64 per entry: d_row_state (R,) = the best column seen so far for every row,
+ * d_col_state (B,) = the best row seen so far for every column.  Entry = (order key of the value << 32) | (0xFFFFFFFF - id);
+ * an empty state is all zero bytes (there is no init entry point).  Order: K17's — NaN first, then the larger value,
+ * -0.0 == +0.0, equal values by the smaller id.  "Better" is the unsigned maximum of the entries, so the states after a sequence
+ * of merges are the maxima of everything seen, bit for bit, whatever the cut into tiles, their order and the scheduling.
+ * The entry does not carry a zero's sign or a NaN's payload: they decode as +0.0 and as the canonical quiet NaN.
+ * Fold a tile: d_cand holds R rows of B fp32 columns, row stride ld >= B elements (any 4-byte aligned start); row r has the id
+ * row_id_base + r, column j the id col_id_base + j, all ids within [0, 2^32 - 2].  The tile is read once and is fully
+ * consumed when the stream reaches the end of this call.  R == 0 or B == 0 is a no-op. */
+int sl_mutualmax_merge(uint64_t* d_row_state, uint64_t* d_col_state, int64_t R, int64_t B, const float* d_cand, int64_t ld,
+                       int64_t row_id_base, int64_t col_id_base, void* stream);
+/* Decode n state entries into K17's k = 1 form: d_vals (n,) fp32 and d_ids (n,) int64; an empty entry gives (-inf, -1). */
+int sl_mutualmax_finish(const uint64_t* d_state, int64_t n, float* d_vals, int64_t* d_ids, void* stream);
+
 /* normalize(x) @ normalize(y)^T for ANY shapes — x (M,K), y (N,K), out (M,N) — with K6's kernels and arithmetic mode
  * (sl_set_gemm_mode) and none of similarity_score's shape branches: what the tiled top-k probing calls per tile.
  * d_ws: sl_cosine_nt_ws_bytes(M,N,K) bytes. */
@@ -499,7 +514,7 @@ size_t sl_cosine_nt_ws_bytes(int64_t M, int64_t N, int64_t K);
 #define SL_PROF_GATHER 3
 #define SL_PROF_SCORES 4
 #define SL_PROF_BATCHNORM 5 /* K16 fused inference BatchNorm; launches = BatchNorm2d evaluations (K19) */
-#define SL_PROF_TOPK 6 /* K17 streaming fp32 top-k */
+#define SL_PROF_TOPK 6 /* K17 streaming fp32 top-k; K20 mutual best matches */
 #define SL_PROF_NFAM 7
 int sl_prof_enable(int on);
 int sl_prof_reset(void);

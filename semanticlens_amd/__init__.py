@@ -9,7 +9,7 @@ HIP device, compute calls raise.
 from __future__ import annotations
 
 from semanticlens_amd import foundation_models, scores, utils
-from semanticlens_amd.lens import Lens
+from semanticlens_amd.lens import ConceptDBComparison, Lens, compare_concept_dbs
 from semanticlens_amd.scores import clarity_score, polysemanticity_score, redundancy_score
 
 __version__ = "0.1.0"
@@ -19,6 +19,8 @@ __all__ = [
     "scores",
     "utils",
     "Lens",
+    "compare_concept_dbs",
+    "ConceptDBComparison",
     "clarity_score",
     "polysemanticity_score",
     "redundancy_score",

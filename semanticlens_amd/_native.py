@@ -123,6 +123,8 @@ SIGNATURES = {
     "sl_topk_merge": (_int, [_vp, _vp, _i64, _i64, _vp, _i64, _i64, _i64, _vp, _sz, _vp]),
     "sl_topk_merge_ws_bytes": (_sz, [_i64, _i64, _i64]),
     "sl_topk_merge_states": (_int, [_vp, _vp, _i64, _i64, _vp, _vp, _i64, _vp]),
+    "sl_mutualmax_merge": (_int, [_vp, _vp, _i64, _i64, _vp, _i64, _i64, _i64, _vp]),
+    "sl_mutualmax_finish": (_int, [_vp, _i64, _vp, _vp, _vp]),
     "sl_cosine_nt": (_int, [_vp, _i64, _vp, _i64, _i64, _vp, _vp, _sz, _vp]),
     "sl_cosine_nt_ws_bytes": (_sz, [_i64, _i64, _i64]),
     "sl_prof_enable": (_int, [_int]),
@@ -925,6 +927,91 @@ def topk_probe(x: torch.Tensor, y: torch.Tensor, k: int, chunk_rows: int | None 
         cosine_nt(xd, yd[start : start + rows], out, ws)
         topk_merge(vals, ids, out, id_base + start, merge_ws)
     return vals, ids
+
+
+# ------------------------------------------------------------------------------------------------
+# K20: mutual best matches (row and column maxima of every cosine tile in one read)
+# ------------------------------------------------------------------------------------------------
+MUTUALMAX_MAX_ID = (1 << 32) - 2  # a packed state entry holds a 32-bit id; 2^32 - 1 is left out
+
+
+def _check_mutualmax_state(what: str, state: torch.Tensor, n: int | None = None):
+    if state.ndim != 1 or state.dtype != torch.int64 or not state.is_cuda or (state.numel() > 1 and state.stride(0) != 1):
+        raise ValueError(f"{what}: a state is a 1-D int64 device tensor with unit stride, got {tuple(state.shape)} {state.dtype} on "
+                         f"{state.device}")
+    if n is not None and state.shape[0] != n:
+        raise ValueError(f"{what}: a state of {state.shape[0]} entries does not fit {n}")
+
+
+def mutualmax_merge(row_state: torch.Tensor, col_state: torch.Tensor, cand: torch.Tensor, row_id_base: int = 0, col_id_base: int = 0):
+    """Fold the ``(R, B)`` fp32 tile ``cand`` (unit column stride, any row stride) into ``row_state (R,)`` — the best column of
+    every row — and ``col_state (B,)`` — the best row of every column — in one read of the tile.  States are int64 tensors of
+    packed entries (``torch.zeros`` is the empty state; decode with ``mutualmax_finish``); row ``r`` has the id
+    ``row_id_base + r``, column ``j`` the id ``col_id_base + j``, all within ``[0, MUTUALMAX_MAX_ID]``."""
+    if cand.ndim != 2 or cand.dtype != torch.float32 or not cand.is_cuda:
+        raise ValueError(f"mutualmax_merge: the candidate tile must be a 2-D float32 device tensor, got {tuple(cand.shape)} {cand.dtype}")
+    R, B = cand.shape
+    _check_mutualmax_state("mutualmax_merge", row_state, R)
+    _check_mutualmax_state("mutualmax_merge", col_state, B)
+    if B > 1 and cand.stride(1) != 1:
+        cand = cand.contiguous()
+    ld = cand.stride(0) if R > 1 else B
+    if ld < B:
+        cand, ld = cand.contiguous(), B
+    with _on(cand.device):
+        rc = lib().sl_mutualmax_merge(_ptr(row_state), _ptr(col_state), R, B, _ptr(cand), ld, row_id_base, col_id_base, _stream(cand))
+    _check(rc, "sl_mutualmax_merge")
+
+
+def mutualmax_finish(state: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
+    """Decode a packed state into K17's ``k = 1`` form: ``(values (n,) float32, ids (n,) int64)``, ``(-inf, -1)`` where nothing
+    was seen.  A zero comes back as ``+0.0`` and a NaN as the canonical quiet NaN, whatever went in."""
+    _check_mutualmax_state("mutualmax_finish", state)
+    n = state.shape[0]
+    vals = torch.empty(n, dtype=torch.float32, device=state.device)
+    ids = torch.empty(n, dtype=torch.int64, device=state.device)
+    with _on(state.device):
+        _check(lib().sl_mutualmax_finish(_ptr(state), n, _ptr(vals), _ptr(ids), _stream(state)), "sl_mutualmax_finish")
+    return vals, ids
+
+
+def mutual_probe(x: torch.Tensor, y: torch.Tensor, chunk_rows: int | None = None, chunk_cols: int | None = None):
+    """Best cosine match in both directions from ONE pass over ``normalize(x) @ normalize(y).T``:
+    ``((x_vals (len(x),), x_ids), (y_vals (len(y),), y_ids))`` — for every row of ``x`` its best row of ``y`` (``x_ids`` index
+    ``y``) and for every row of ``y`` its best row of ``x`` (``y_ids`` index ``x``).  Order as in ``topk_probe``: NaN first,
+    then the larger cosine, equal cosines by the smaller id; ``(-inf, -1)`` when the other operand is empty.
+
+    The cosine GEMM (K6, in the arithmetic ``set_gemm_mode`` selects) writes one reused tile of ``chunk_rows`` rows of ``x``
+    against ``chunk_cols`` rows of ``y`` and K20 folds its row and column maxima into two states on the same stream; the
+    ``(len(x), len(y))`` matrix never exists.  By default a tile spans all of ``y`` and as many rows of ``x`` as keep it at or
+    under ``TOPK_TILE_BYTES``; ``y`` is cut too only where a single row of the tile would pass that size."""
+    if x.ndim != 2 or y.ndim != 2:
+        raise ValueError("mutual_probe expects 2-D tensors")
+    if y.shape[1] != x.shape[1]:
+        raise ValueError(f"embedding widths differ: {x.shape[1]} vs {y.shape[1]}")
+    for name, chunk in (("chunk_rows", chunk_rows), ("chunk_cols", chunk_cols)):
+        if chunk is not None and chunk < 1:
+            raise ValueError(f"{name} = {chunk} must be at least 1")
+    if max(x.shape[0], y.shape[0]) > MUTUALMAX_MAX_ID + 1:
+        raise ValueError(f"mutual_probe: more than {MUTUALMAX_MAX_ID + 1} rows do not fit a packed state's 32-bit ids")
+    xd = _f32c(x)
+    yd = _f32c(y, xd.device)
+    m, n = xd.shape[0], yd.shape[0]
+    row_state = torch.zeros(m, dtype=torch.int64, device=xd.device)
+    col_state = torch.zeros(n, dtype=torch.int64, device=xd.device)
+    if m and n:
+        cols = min(chunk_cols or min(n, TOPK_TILE_BYTES // 4), n)
+        rows = min(chunk_rows or topk_chunk_rows(cols, m), m)  # rows of a (rows, cols) tile at or under the tile size
+        tile = torch.empty(rows * cols, dtype=torch.float32, device=xd.device)
+        ws = torch.empty(int(lib().sl_cosine_nt_ws_bytes(rows, cols, xd.shape[1])), dtype=torch.uint8, device=xd.device)
+        for r0 in range(0, m, rows):
+            nr = min(rows, m - r0)
+            for c0 in range(0, n, cols):
+                nc = min(cols, n - c0)
+                out = tile[: nr * nc].view(nr, nc)
+                cosine_nt(xd[r0 : r0 + nr], yd[c0 : c0 + nc], out, ws)
+                mutualmax_merge(row_state[r0 : r0 + nr], col_state[c0 : c0 + nc], out, r0, c0)
+    return mutualmax_finish(row_state), mutualmax_finish(col_state)
 
 
 # ------------------------------------------------------------------------------------------------

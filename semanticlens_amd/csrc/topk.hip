@@ -30,14 +30,7 @@ constexpr int64_t kMinSegment = 1024;  // columns per wave when a row is split
 
 typedef float f4 __attribute__((ext_vector_type(4)));
 
-// monotone 32-bit key of an fp32: larger key == ranks earlier.  NaN -> all ones, -0.0 -> +0.0's key; every real value's key
-// is >= 0x007FFFFF (-inf), so 0 is free for the empty slot
-__device__ inline uint32_t f32_order_key(float v) {
-  const uint32_t u = f32_bits(v);
-  if ((u & 0x7FFFFFFFu) > 0x7F800000u) return 0xFFFFFFFFu;
-  if (u == 0x80000000u) return 0x80000000u;
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
+// f32_order_key (common.hpp) of a slot; the empty slot's key is 0, below every real value's
 __device__ inline uint32_t entry_key(float v, int64_t id) { return id < 0 ? 0u : f32_order_key(v); }
 
 // One wavefront's selection state in LDS.  Every member function is called by all 64 lanes together.

@@ -10,6 +10,7 @@ from __future__ import annotations
 import os
 
 import logging
+from dataclasses import dataclass
 
 import torch
 from safetensors.torch import load_file, save_file
@@ -297,6 +298,124 @@ def search_components_image(fm, query, aggregated_concept_db, k: int = 10):
     return probe_topk(_embed_image_probe(fm, query), aggregated_concept_db, k, per="query")
 
 
+# ------------------------------------------------------------------------------------------------
+# compare: two concept DBs against each other, both directions from one cosine pass (K6 tiles + K20)
+# ------------------------------------------------------------------------------------------------
+@dataclass
+class ConceptDBComparison:
+    """What ``compare_concept_dbs`` returns.  Every tensor lives on DB A's device.
+
+    * ``layers_a`` / ``layers_b``: the layer names (``[None]`` for a tensor DB); ``sizes_a`` / ``sizes_b``: their component counts.
+    * ``pairs[(i, j)]`` = ``(vals_a (Ca,), ids_a (Ca,), vals_b (Cb,), ids_b (Cb,))`` for A's layer ``i`` and B's layer ``j``: every
+      A component's best cosine in that B layer and the B component that has it, and the reverse.  ``pair(name_a, name_b)`` reads
+      it by name.
+    * ``best_ab[i]`` = ``(values (Ca,), ids (Ca,))``: every component of A's layer ``i`` against ALL of B, ``ids`` being B's global
+      component ids ``offset[layer] + component``; ``best_ba[j]`` the reverse.  ``best_in_b`` / ``best_in_a`` decode them.
+
+    A NaN cosine (a NaN in an embedding) ranks before every number, so it becomes the best match of its row and column and
+    turns the means it enters into NaN; nothing filters it."""
+
+    layers_a: list
+    layers_b: list
+    sizes_a: list[int]
+    sizes_b: list[int]
+    pairs: dict
+    best_ab: list
+    best_ba: list
+
+    def pair(self, name_a=None, name_b=None):
+        """``(vals_a, ids_a, vals_b, ids_b)`` of one layer pair."""
+        return self.pairs[(self.layers_a.index(name_a), self.layers_b.index(name_b))]
+
+    def _layer_similarity(self, side: int) -> torch.Tensor:
+        La, Lb = len(self.layers_a), len(self.layers_b)
+        rows = [[self.pairs[(i, j)][side].mean() for j in range(Lb)] for i in range(La)]
+        if side:  # the pair's B -> A half: (Lb, La)
+            rows = [[rows[i][j] for i in range(La)] for j in range(Lb)]
+        return torch.stack([torch.stack(r) for r in rows])
+
+    @property
+    def layer_similarity_ab(self) -> torch.Tensor:
+        """``(La, Lb)`` float32: the mean over an A layer's components of their best cosine in a B layer."""
+        return self._layer_similarity(0)
+
+    @property
+    def layer_similarity_ba(self) -> torch.Tensor:
+        """``(Lb, La)`` float32: the mean over a B layer's components of their best cosine in an A layer."""
+        return self._layer_similarity(2)
+
+    @property
+    def set_similarity_ab(self) -> float:
+        """``mean_i max_j cos(a_i, b_j)`` over ALL of A's components against all of B (fp32 mean on the device)."""
+        return float(torch.cat([v for v, _ in self.best_ab]).mean())
+
+    @property
+    def set_similarity_ba(self) -> float:
+        return float(torch.cat([v for v, _ in self.best_ba]).mean())
+
+    @property
+    def best_in_b(self) -> dict:
+        """``{name_a: (values (Ca,), layer_index (Ca,), component (Ca,))}``: the best match across all of B's layers (ties between
+        layers go to the earlier layer, then to the smaller component)."""
+        return {name: (v,) + _decode_layers(g, self.sizes_b) for name, (v, g) in zip(self.layers_a, self.best_ab)}
+
+    @property
+    def best_in_a(self) -> dict:
+        return {name: (v,) + _decode_layers(g, self.sizes_a) for name, (v, g) in zip(self.layers_b, self.best_ba)}
+
+    def mutual(self) -> dict:
+        """``{name_a: bool (Ca,)}``: component ``a``'s best match in B has ``a`` as ITS best match in A (mutual nearest neighbours)."""
+        to_b = torch.cat([g for _, g in self.best_ab])  # per global A id: its best global B id
+        to_a = torch.cat([g for _, g in self.best_ba])
+        back = to_a[to_b.clamp(min=0)]
+        mask = (to_b >= 0) & (back == torch.arange(to_b.numel(), device=to_b.device))
+        return dict(zip(self.layers_a, mask.split(self.sizes_a)))
+
+
+def _merge_best(per_layer, offsets):
+    """The best of several layers' ``k = 1`` results ``[(vals (C,), ids (C,)), ...]`` under K17's order, as ``(values (C,), global
+    ids (C,))`` with ``global id = offsets[layer] + id``."""
+    C, dev = per_layer[0][0].shape[0], per_layer[0][0].device
+    vals, ids = N.topk_new(C, 1, dev)
+    other_v = torch.stack([v for v, _ in per_layer], dim=1)
+    other_i = torch.stack([torch.where(i < 0, i, i + off) for (_, i), off in zip(per_layer, offsets)], dim=1)
+    N.topk_merge_states(vals, ids, other_v, other_i)
+    return vals[:, 0], ids[:, 0]
+
+
+@torch.no_grad()
+def compare_concept_dbs(aggregated_concept_db_a, aggregated_concept_db_b, chunk_rows: int | None = None) -> ConceptDBComparison:
+    """Compare two aggregated concept DBs (``(C, D)`` tensors or dicts of layers) embedded by the same foundation model: which
+    components of A have a counterpart in B and the reverse, and how similar each layer of A is to each layer of B — the
+    directed set similarity ``S(A -> B) = mean_i max_j cos(a_i, b_j)`` per layer pair and overall, in both directions.
+
+    One ``_native.mutual_probe`` per layer pair: the cosine GEMM writes one tile at a time and K20 takes the row maxima (A -> B)
+    and the column maxima (B -> A) out of the same read, so each product is computed once and no ``(Ca, Cb)`` matrix exists.
+    The best match across layers is a merge of the per-pair results under the order of ``probe_topk``.  Always
+    ``normalize(a) @ normalize(b).T``.  Shapes are checked before a device is touched; see ``ConceptDBComparison``."""
+    names_a, layers_a, _ = _db_layers(aggregated_concept_db_a)
+    names_b, layers_b, _ = _db_layers(aggregated_concept_db_b)
+    for what, layers in (("A", layers_a), ("B", layers_b)):
+        if not layers or any(layer.shape[0] == 0 for layer in layers):
+            raise ValueError(f"concept DB {what} is empty (no layers, or a layer without components)")
+    _check_width(layers_b[0], layers_a)
+    da = [N._f32c(layer) for layer in layers_a]
+    db = [N._f32c(layer, da[0].device) for layer in layers_b]
+    out_dev = layers_a[0].device
+    sizes_a, sizes_b = [t.shape[0] for t in da], [t.shape[0] for t in db]
+    pairs = {(i, j): N.mutual_probe(a, b, chunk_rows) for i, a in enumerate(da) for j, b in enumerate(db)}
+    off_a = [sum(sizes_a[:i]) for i in range(len(da))]
+    off_b = [sum(sizes_b[:j]) for j in range(len(db))]
+    best_ab = [_merge_best([pairs[(i, j)][0] for j in range(len(db))], off_b) for i in range(len(da))]
+    best_ba = [_merge_best([pairs[(i, j)][1] for i in range(len(da))], off_a) for j in range(len(db))]
+    to = lambda ts: tuple(t.to(out_dev) for t in ts)
+    return ConceptDBComparison(
+        layers_a=names_a, layers_b=names_b, sizes_a=sizes_a, sizes_b=sizes_b,
+        pairs={key: to(ab + ba) for key, (ab, ba) in pairs.items()},
+        best_ab=[to(t) for t in best_ab], best_ba=[to(t) for t in best_ba],
+    )
+
+
 class Lens:
     """Holds the foundation model and wraps the workflow (reference: lens.py:217-480)."""
 
@@ -354,6 +473,9 @@ class Lens:
 
     def search_components_image(self, query, aggregated_concept_db, k=10):
         return search_components_image(self.fm, query, aggregated_concept_db, k)
+
+    def compare_concept_dbs(self, aggregated_concept_db_a, aggregated_concept_db_b, chunk_rows=None):
+        return compare_concept_dbs(aggregated_concept_db_a, aggregated_concept_db_b, chunk_rows)
 
     @staticmethod
     def _per_layer(fn, db):
