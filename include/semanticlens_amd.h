@@ -284,6 +284,25 @@ int sl_polykmeans(const float* d_V, int64_t C, int64_t n, int64_t D, int n_clust
                   size_t ws_bytes, void* stream);
 size_t sl_polykmeans_ws_bytes(int64_t C, int64_t n, int64_t D, int n_clusters, int n_init);
 
+/* ---- K21: facets — the clustering K9's score comes from, and what describe / search need of it -------------------------
+ * sl_poly2means_labels / sl_polykmeans_labels: sl_poly2means / sl_polykmeans plus d_labels (C,n) int32: row c is
+ * scikit-learn's `labels_` (scores.py:167) of the run component c's score comes from, after the final E-step; cluster j is
+ * the j-th seeded centre.  Every other output is bit-identical to the call without labels; same workspace. */
+int sl_poly2means_labels(const float* d_V, int64_t C, int64_t n, int64_t D, const int32_t* h_first_center, int n_init,
+                         const double* h_rand, int replace_empty_clusters, double* d_out, int32_t* d_min_count,
+                         int32_t* d_labels, void* d_ws, size_t ws_bytes, void* stream);
+int sl_polykmeans_labels(const float* d_V, int64_t C, int64_t n, int64_t D, int n_clusters, const int32_t* h_first_center,
+                         int n_init, const double* h_rand, int replace_empty_clusters, double* d_out, int32_t* d_min_count,
+                         int32_t* d_labels, void* d_ws, size_t ws_bytes, void* stream);
+/* V (C,n,D) fp32, labels (C,n) int32 -> per component and cluster j in [0,kc):
+ *   counts (C,kc) int32, centres (C,kc,D) fp32 = mean of the RAW rows with label j (what scores.py:168 reads as
+ *   `cluster_centers_`), clarity (C,kc) fp32 = clarity_score of those rows (may be NULL).
+ * A label outside [0,kc) belongs to no facet and is skipped (lets a caller mask samples).
+ * count 0: centre row = zeros, clarity NaN.  count 1: clarity NaN.
+ * 1 <= kc <= 16, n <= 1024, any D >= 1.  One read of V; results do not depend on the grid; no float atomics. */
+int sl_facet_stats(const float* d_V, int64_t C, int64_t n, int64_t D, const int32_t* d_labels, int n_clusters,
+                   float* d_centres, int32_t* d_counts, float* d_clarity, void* stream);
+
 /* ---- K10: template-difference mean of text embeddings (lens.py:196-199) ------------------
  * E (Q*T,D) read as "(q t) d", E0 (T,D); out (Q,D) = mean_t(E[q,t] - E0[t]). */
 int sl_template_mean(const float* d_E, const float* d_E0, int64_t Q, int64_t T, int64_t D, float* d_out,

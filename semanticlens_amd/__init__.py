@@ -9,8 +9,8 @@ HIP device, compute calls raise.
 from __future__ import annotations
 
 from semanticlens_amd import foundation_models, scores, utils
-from semanticlens_amd.lens import ConceptDBComparison, Lens, compare_concept_dbs
-from semanticlens_amd.scores import clarity_score, polysemanticity_score, redundancy_score
+from semanticlens_amd.lens import ConceptDBComparison, Lens, compare_concept_dbs, label_facets, search_facets
+from semanticlens_amd.scores import Facets, clarity_score, polysemanticity_facets, polysemanticity_score, redundancy_score
 
 __version__ = "0.1.0"
 
@@ -24,4 +24,8 @@ __all__ = [
     "clarity_score",
     "polysemanticity_score",
     "redundancy_score",
+    "Facets",
+    "polysemanticity_facets",
+    "label_facets",
+    "search_facets",
 ]

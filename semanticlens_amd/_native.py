@@ -90,6 +90,9 @@ SIGNATURES = {
     "sl_kmeans_trials": (_int, [_int]),
     "sl_polykmeans": (_int, [_vp, _i64, _i64, _i64, _int, _vp, _int, _vp, _int, _vp, _vp, _vp, _sz, _vp]),
     "sl_polykmeans_ws_bytes": (_sz, [_i64, _i64, _i64, _int, _int]),
+    "sl_poly2means_labels": (_int, [_vp, _i64, _i64, _i64, _vp, _int, _vp, _int, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "sl_polykmeans_labels": (_int, [_vp, _i64, _i64, _i64, _int, _vp, _int, _vp, _int, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "sl_facet_stats": (_int, [_vp, _i64, _i64, _i64, _vp, _int, _vp, _vp, _vp, _vp]),
     "sl_linear": (_int, [_vp, _i64, _i64, _vp, _i64, _vp, _int, _vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp]),
     "sl_layernorm": (_int, [_vp, _i64, _i64, _i64, _vp, _vp, ctypes.c_float, _vp, _vp, _i64, _vp]),
     "sl_attention": (_int, [_vp, _i64, _i64, _i64, _i64, _int, _vp, _vp, _vp]),
@@ -1127,8 +1130,51 @@ def _poly_ws_budget() -> int:
     return int(float(os.environ.get("SL_POLY_WS_GB", "8")) * (1 << 30))
 
 
-def poly2means(V: torch.Tensor, first_center, rand, replace_empty_clusters: bool = True, n_clusters: int = 2) -> torch.Tensor:
+FACET_MAX_CLUSTERS = 16  # sl_facet_stats: n_clusters (kMaxFacets in csrc/facets.hip)
+FACET_MAX_N = 1024       # sl_facet_stats: samples per component
+
+
+def _facet_stats_into(Vd: torch.Tensor, labels: torch.Tensor, n_clusters: int, centres, counts, clarity):
+    """One ``sl_facet_stats`` call on contiguous device tensors; the caller holds the device guard."""
+    C, n, D = Vd.shape
+    rc = lib().sl_facet_stats(_ptr(Vd), C, n, D, _ptr(labels), int(n_clusters), _ptr(centres), _ptr(counts), _ptr(clarity), _stream(Vd))
+    _check(rc, "sl_facet_stats")
+
+
+def facet_stats(V: torch.Tensor, labels: torch.Tensor, n_clusters: int, clarity: bool = True):
+    """K21: per component of ``V (C, n, D)`` and cluster ``j`` of ``labels (C, n)``: ``(centres (C, kc, D) float32 — the mean of
+    the raw rows with label ``j`` —, counts (C, kc) int32, clarity (C, kc) float32 or None)``, on the device.  A label outside
+    ``[0, n_clusters)`` belongs to no facet; an empty facet has a zero centre, a facet of fewer than two rows a NaN clarity."""
+    if V.ndim != 3 or labels.ndim != 2 or tuple(labels.shape) != tuple(V.shape[:2]):
+        raise ValueError(f"facet_stats expects V (C, n, D) and labels (C, n), got {tuple(V.shape)} and {tuple(labels.shape)}")
+    if not 1 <= n_clusters <= FACET_MAX_CLUSTERS:
+        raise ValueError(f"n_clusters={n_clusters} not in [1, {FACET_MAX_CLUSTERS}]")
+    if V.shape[1] > FACET_MAX_N:
+        raise ValueError(f"n_samples={V.shape[1]} exceeds the device kernel's maximum of {FACET_MAX_N} samples per component")
+    Vd = _f32c(V)
+    ld = to_device(labels, Vd.device).to(torch.int32).contiguous()
+    C, n, D = Vd.shape
+    centres = torch.empty((C, n_clusters, D), dtype=torch.float32, device=Vd.device)
+    counts = torch.empty((C, n_clusters), dtype=torch.int32, device=Vd.device)
+    clar = torch.empty((C, n_clusters), dtype=torch.float32, device=Vd.device) if clarity else None
+    if C and n and D:
+        with _on(Vd.device):
+            _facet_stats_into(Vd, ld, n_clusters, centres, counts, clar)
+    else:  # nothing to read: every facet is empty
+        centres.zero_()
+        counts.zero_()
+        if clar is not None:
+            clar.fill_(float("nan"))
+    return centres, counts, clar
+
+
+def poly2means(V: torch.Tensor, first_center, rand, replace_empty_clusters: bool = True, n_clusters: int = 2, labels=None,
+               stats=None) -> torch.Tensor:
     """polysemanticity of V (C,n,D): k-means per component on the device; float64 (C,) result.
+
+    ``labels``: a ``(C, n)`` int32 device tensor that receives scikit-learn's ``labels_`` of the clustering each score comes
+    from (K21; ``sl_*_labels``).  ``stats``: with ``labels``, ``(centres (C, kc, D) f32, counts (C, kc) i32, clarity (C, kc) f32)``
+    device tensors filled by ``sl_facet_stats`` chunk by chunk, right behind the chunk's clustering.
 
     Any number of components: calls are chunked by the Gram kernel's grid limit (65 535 components) and by the workspace
     budget.  ``n_samples > 1024`` with ``n_clusters != 2`` (or > 128 samples), and ``n_clusters > 16``, raise
@@ -1144,6 +1190,10 @@ def poly2means(V: torch.Tensor, first_center, rand, replace_empty_clusters: bool
     n_init = int(first_center.shape[0])
     out = torch.empty((C,), dtype=torch.float64, device=Vd.device)
     mincnt = torch.empty((C,), dtype=torch.int32, device=Vd.device)
+    if labels is not None and not (labels.is_cuda and labels.dtype == torch.int32 and labels.is_contiguous() and tuple(labels.shape) == (C, n)):
+        raise ValueError(f"labels must be a contiguous ({C}, {n}) int32 device tensor")
+    if stats is not None and labels is None:
+        raise ValueError("stats are computed from the labels: pass labels too")
     general = n_clusters != 2 or n > POLY2_MAX_N
     if general:
         if n_clusters > POLYK_MAX_CLUSTERS:
@@ -1159,27 +1209,34 @@ def poly2means(V: torch.Tensor, first_center, rand, replace_empty_clusters: bool
         for c0 in range(0, C, chunk):
             cc = min(chunk, C - c0)
             Vc, oc, mc = Vd[c0:c0 + cc], out[c0:c0 + cc], mincnt[c0:c0 + cc]
+            lc = labels[c0:c0 + cc] if labels is not None else None
             if general:
                 nbytes = int(lib().sl_polykmeans_ws_bytes(cc, n, D, n_clusters, n_init))
                 if ws is None or ws.numel() < nbytes:
                     ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=Vd.device)
-                rc = lib().sl_polykmeans(
-                    _ptr(Vc), cc, n, D, int(n_clusters), first_center.ctypes.data_as(_vp), n_init, rand.ctypes.data_as(_vp),
-                    1 if replace_empty_clusters else 0, _ptr(oc), _ptr(mc), _ptr(ws), nbytes, _stream(Vd),
-                )
+                args = (_ptr(Vc), cc, n, D, int(n_clusters), first_center.ctypes.data_as(_vp), n_init, rand.ctypes.data_as(_vp),
+                        1 if replace_empty_clusters else 0, _ptr(oc), _ptr(mc))
+                if lc is None:
+                    rc = lib().sl_polykmeans(*args, _ptr(ws), nbytes, _stream(Vd))
+                else:
+                    rc = lib().sl_polykmeans_labels(*args, _ptr(lc), _ptr(ws), nbytes, _stream(Vd))
                 torch.cuda.current_stream(Vd.device).synchronize()  # the draws were copied from host arrays owned by this call
                 _check(rc, "sl_polykmeans")
             else:
                 nbytes = int(lib().sl_poly2means_ws_bytes(cc, n, D))
                 if ws is None or ws.numel() < nbytes:
                     ws = torch.empty(nbytes, dtype=torch.uint8, device=Vd.device)
-                rc = lib().sl_poly2means(
-                    _ptr(Vc), cc, n, D, first_center.ctypes.data_as(_vp), n_init, rand.ctypes.data_as(_vp),
-                    1 if replace_empty_clusters else 0, _ptr(oc), _ptr(mc), _ptr(ws), nbytes, _stream(Vd),
-                )
+                args = (_ptr(Vc), cc, n, D, first_center.ctypes.data_as(_vp), n_init, rand.ctypes.data_as(_vp),
+                        1 if replace_empty_clusters else 0, _ptr(oc), _ptr(mc))
+                if lc is None:
+                    rc = lib().sl_poly2means(*args, _ptr(ws), nbytes, _stream(Vd))
+                else:
+                    rc = lib().sl_poly2means_labels(*args, _ptr(lc), _ptr(ws), nbytes, _stream(Vd))
                 if rc == -3:
                     raise NotImplementedError(lib().sl_last_error().decode())
                 _check(rc, "sl_poly2means")
+            if stats is not None:
+                _facet_stats_into(Vc, lc, n_clusters, *(t[c0:c0 + cc] for t in stats))
     return out
 
 

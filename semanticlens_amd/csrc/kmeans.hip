@@ -165,7 +165,7 @@ struct Work {
 
 __global__ __launch_bounds__(64) void kmeans2_kernel(const double* __restrict__ Hall, int64_t C, int n, int64_t D,
                                                       Draws dr, int replace_empty, double* __restrict__ out,
-                                                      int32_t* __restrict__ min_count) {
+                                                      int32_t* __restrict__ min_count, int32_t* __restrict__ labels) {
   extern __shared__ __align__(16) unsigned char smem[];
   const int lane = threadIdx.x;
   const int64_t c = blockIdx.x;
@@ -351,6 +351,10 @@ __global__ __launch_bounds__(64) void kmeans2_kernel(const double* __restrict__ 
     __syncthreads();
   }
 
+  // K21: scikit-learn's `labels_` of the chosen run (scores.py:167), cluster j = the j-th seeded centre
+  if (labels)
+    for (int i = lane; i < n; i += kWave) labels[c * n + i] = w.best_label[i];
+
   // ---- scores.py:168-185 on the chosen clustering ----
   // centres c_k = mean_{j in S_k} x_j;  x_i . x_j = H_ij
   double cA = 0.0, cB = 0.0, dAA = 0.0, dBB = 0.0, dAB = 0.0;
@@ -435,7 +439,8 @@ __host__ __device__ inline size_t gen_ws_bytes_per_component(int64_t n, int64_t 
 __global__ __launch_bounds__(64) void kmeansk_kernel(const double* __restrict__ Hall, int64_t C, int n, int64_t D, int k, int trials,
                                                       int n_init, const int32_t* __restrict__ first, const double* __restrict__ rnd,
                                                       int replace_empty, unsigned char* __restrict__ ws_all, size_t ws_stride,
-                                                      double* __restrict__ out, int32_t* __restrict__ min_count) {
+                                                      double* __restrict__ out, int32_t* __restrict__ min_count,
+                                                      int32_t* __restrict__ labels) {
   __shared__ double s_acc[kMaxClusters * kWave];  // per-lane accumulators, one column per lane
   __shared__ double s_cnt[kMaxClusters], s_W[kMaxClusters], s_ncnt[kMaxClusters], s_nW[kMaxClusters], s_x[kMaxClusters];
   __shared__ double s_dot[kMaxClusters * kMaxClusters];
@@ -697,6 +702,9 @@ __global__ __launch_bounds__(64) void kmeansk_kernel(const double* __restrict__ 
     __syncthreads();
   }
 
+  if (labels)  // K21: scikit-learn's `labels_` of the chosen run, as in kmeans2_kernel
+    for (int i = lane; i < n; i += kWave) labels[c * n + i] = w.best_label[i];
+
   // ---- scores.py:168-185 on the chosen clustering: 1 - clarity(centres), clarity over the k centre vectors ----
   // original-space centres c_j = centred centre + mean:  c_j.c_l = g_jl + (R_j - mu) + (R_l - mu) + mu, with
   // g_jl = sum_{a in S_j} s_l[a] / (n_j n_l) (centred) and R_j = mean_{a in S_j} r_a, r_a = mean_b H_ab
@@ -812,9 +820,9 @@ SL_API size_t sl_poly2means_ws_bytes(int64_t C, int64_t n, int64_t D) {
   return (size_t)C * (size_t)n * (size_t)n * 8 + 256;
 }
 
-SL_API int sl_poly2means(const float* d_V, int64_t C, int64_t n, int64_t D, const int32_t* h_first_center, int n_init,
-                         const double* h_rand, int replace_empty_clusters, double* d_out, int32_t* d_min_count,
-                         void* d_ws, size_t ws_bytes, void* stream) {
+static int poly2means_impl(const float* d_V, int64_t C, int64_t n, int64_t D, const int32_t* h_first_center, int n_init,
+                           const double* h_rand, int replace_empty_clusters, double* d_out, int32_t* d_min_count,
+                           int32_t* d_labels, void* d_ws, size_t ws_bytes, void* stream) {
   SL_REQUIRE(C >= 0 && n >= 0 && D >= 0, "sl_poly2means: negative shape");
   if (C == 0) return 0;
   SL_REQUIRE(n >= 2, "sl_poly2means: n_samples=%lld should be >= n_clusters=2.", (long long)n);  // sklearn's ValueError
@@ -846,9 +854,24 @@ SL_API int sl_poly2means(const float* d_V, int64_t C, int64_t n, int64_t D, cons
   if (smem > 64 * 1024)
     SL_CHECK_HIP(hipFuncSetAttribute((const void*)kmeans2_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
   hipLaunchKernelGGL(kmeans2_kernel, dim3((unsigned)C), dim3(64), smem, st, (const double*)H, C, (int)n, D, dr,
-                     replace_empty_clusters, d_out, d_min_count);
+                     replace_empty_clusters, d_out, d_min_count, d_labels);
   SL_CHECK_HIP(hipGetLastError());
   return 0;
+}
+
+SL_API int sl_poly2means(const float* d_V, int64_t C, int64_t n, int64_t D, const int32_t* h_first_center, int n_init,
+                         const double* h_rand, int replace_empty_clusters, double* d_out, int32_t* d_min_count,
+                         void* d_ws, size_t ws_bytes, void* stream) {
+  return poly2means_impl(d_V, C, n, D, h_first_center, n_init, h_rand, replace_empty_clusters, d_out, d_min_count, nullptr, d_ws,
+                         ws_bytes, stream);
+}
+
+SL_API int sl_poly2means_labels(const float* d_V, int64_t C, int64_t n, int64_t D, const int32_t* h_first_center, int n_init,
+                                const double* h_rand, int replace_empty_clusters, double* d_out, int32_t* d_min_count,
+                                int32_t* d_labels, void* d_ws, size_t ws_bytes, void* stream) {
+  SL_REQUIRE(d_labels || C <= 0 || n <= 0, "sl_poly2means_labels: null label pointer");
+  return poly2means_impl(d_V, C, n, D, h_first_center, n_init, h_rand, replace_empty_clusters, d_out, d_min_count, d_labels, d_ws,
+                         ws_bytes, stream);
 }
 
 // ---- any n_clusters / larger n: the general kernel ---------------------------------------------------------------------
@@ -861,9 +884,9 @@ SL_API size_t sl_polykmeans_ws_bytes(int64_t C, int64_t n, int64_t D, int n_clus
   return (size_t)C * (size_t)n * (size_t)n * 8 + (size_t)C * gen_ws_bytes_per_component(n, n_clusters) + ((draws + 255) & ~(size_t)255) + 512;
 }
 
-SL_API int sl_polykmeans(const float* d_V, int64_t C, int64_t n, int64_t D, int n_clusters, const int32_t* h_first_center,
-                         int n_init, const double* h_rand, int replace_empty_clusters, double* d_out, int32_t* d_min_count,
-                         void* d_ws, size_t ws_bytes, void* stream) {
+static int polykmeans_impl(const float* d_V, int64_t C, int64_t n, int64_t D, int n_clusters, const int32_t* h_first_center,
+                           int n_init, const double* h_rand, int replace_empty_clusters, double* d_out, int32_t* d_min_count,
+                           int32_t* d_labels, void* d_ws, size_t ws_bytes, void* stream) {
   SL_REQUIRE(C >= 0 && n >= 0 && D >= 0, "sl_polykmeans: negative shape");
   if (C == 0) return 0;
   SL_REQUIRE(n_clusters >= 2 && n_clusters <= kMaxClusters, "sl_polykmeans: n_clusters=%d not in [2, %d]", n_clusters, kMaxClusters);
@@ -896,7 +919,23 @@ SL_API int sl_polykmeans(const float* d_V, int64_t C, int64_t n, int64_t D, int 
     SL_LAUNCH(prof, gram_general_kernel, dim3((unsigned)bx, (unsigned)C), dim3(256), 0, st, d_V, C, (int)n, D, H);
   }
   hipLaunchKernelGGL(kmeansk_kernel, dim3((unsigned)C), dim3(64), 0, st, (const double*)H, C, (int)n, D, n_clusters, trials, n_init,
-                     (const int32_t*)d_first, (const double*)d_rand, replace_empty_clusters, slices, stride, d_out, d_min_count);
+                     (const int32_t*)d_first, (const double*)d_rand, replace_empty_clusters, slices, stride, d_out, d_min_count,
+                     d_labels);
   SL_CHECK_HIP(hipGetLastError());
   return 0;
+}
+
+SL_API int sl_polykmeans(const float* d_V, int64_t C, int64_t n, int64_t D, int n_clusters, const int32_t* h_first_center,
+                         int n_init, const double* h_rand, int replace_empty_clusters, double* d_out, int32_t* d_min_count,
+                         void* d_ws, size_t ws_bytes, void* stream) {
+  return polykmeans_impl(d_V, C, n, D, n_clusters, h_first_center, n_init, h_rand, replace_empty_clusters, d_out, d_min_count,
+                         nullptr, d_ws, ws_bytes, stream);
+}
+
+SL_API int sl_polykmeans_labels(const float* d_V, int64_t C, int64_t n, int64_t D, int n_clusters, const int32_t* h_first_center,
+                                int n_init, const double* h_rand, int replace_empty_clusters, double* d_out, int32_t* d_min_count,
+                                int32_t* d_labels, void* d_ws, size_t ws_bytes, void* stream) {
+  SL_REQUIRE(d_labels || C <= 0 || n <= 0, "sl_polykmeans_labels: null label pointer");
+  return polykmeans_impl(d_V, C, n, D, n_clusters, h_first_center, n_init, h_rand, replace_empty_clusters, d_out, d_min_count,
+                         d_labels, d_ws, ws_bytes, stream);
 }

@@ -19,7 +19,8 @@ from tqdm.auto import tqdm
 from semanticlens_amd import _native as N
 from semanticlens_amd.component_visualization.base import AbstractComponentVisualizer
 from semanticlens_amd.foundation_models.base import AbstractVLM
-from semanticlens_amd.scores import clarity_score, polysemanticity_score, redundancy_score, similarity_score
+from semanticlens_amd.scores import (Facets, clarity_score, polysemanticity_facets, polysemanticity_score, redundancy_score,
+                                     similarity_score)
 from semanticlens_amd.utils.helper import get_fallback_name
 
 logger = logging.getLogger(__name__)
@@ -299,6 +300,69 @@ def search_components_image(fm, query, aggregated_concept_db, k: int = 10):
 
 
 # ------------------------------------------------------------------------------------------------
+# facets: describe / search the meanings of a polysemantic component (K9's labels + K21)
+# ------------------------------------------------------------------------------------------------
+def _facet_layers(facets):
+    """``(names, [Facets], is_dict)`` of a ``Facets`` or a dict of them."""
+    is_dict = not isinstance(facets, Facets)
+    if is_dict and not isinstance(facets, dict):
+        raise ValueError(f"facets must be a Facets or a dict of them, got {type(facets).__name__}")
+    names = list(facets) if is_dict else [None]
+    layers = [facets[n] for n in names] if is_dict else [facets]
+    for name, f in zip(names, layers):
+        if not isinstance(f, Facets) or f.centers.ndim != 3 or tuple(f.counts.shape) != tuple(f.centers.shape[:2]):
+            raise ValueError(f"layer {name!r} is not a Facets with centers (C, kc, D) and counts (C, kc)")
+    return names, layers, is_dict
+
+
+@torch.no_grad()
+def label_facets(fm, vocabulary: list[str], facets, k: int = 5, templates: list[str] | None = None, batch_size: int | None = None,
+                 chunk_size: int | None = None):
+    """For every facet of every component, its ``k`` best labels out of ``vocabulary``: ``(values (C, kc, k) float32, ids
+    (C, kc, k) int64)`` for a ``Facets``, a dict of such pairs for a dict of them.  It is ``label_components`` on
+    ``facets.aggregated()``, reshaped; the slots of an empty facet (``count == 0``: its centre is all zeros, its cosines mean
+    nothing) hold ``-inf`` / ``-1``, the unused-slot convention of ``probe_topk``."""
+    names, layers, is_dict = _facet_layers(facets)
+    db = {i: f.aggregated() for i, f in enumerate(layers)}
+    labelled = label_components(fm, vocabulary, db, k, templates, batch_size, chunk_size)  # checks its arguments first
+    out = {}
+    for i, (name, f) in enumerate(zip(names, layers)):
+        vals, ids = labelled[i]
+        C, kc = f.counts.shape
+        vals, ids = vals.reshape(C, kc, -1), ids.reshape(C, kc, -1)
+        empty = (f.counts == 0).to(vals.device)[..., None]
+        out[name] = (vals.masked_fill(empty, float("-inf")), ids.masked_fill(empty, -1))
+    return out if is_dict else out[None]
+
+
+@torch.no_grad()
+def search_facets(fm, query, facets, k: int = 10, templates: list[str] | None = None):
+    """The ``k`` facets that best match each text query across ALL layers: ``(values (Q, k), layer_index (Q, k), component
+    (Q, k), facet (Q, k), layer_names)``.  It is ``search_components`` over the layers' aggregated facet DBs with the row
+    decoded as ``(row // kc, row % kc)``; empty facets are dropped before probing, so they never appear.  Unused slots hold
+    ``-inf`` / ``-1``."""
+    k = N.check_topk_k(k)
+    names, layers, _ = _facet_layers(facets)
+    keeps = [(f.counts.reshape(-1) > 0).nonzero()[:, 0] for f in layers]  # rows of aggregated() that hold a facet
+    db = {i: f.aggregated()[keep.to(f.centers.device)] for i, (f, keep) in enumerate(zip(layers, keeps))}
+    vals, layer_index, row, _ = search_components(fm, query, db, k, templates)
+    dev = row.device
+    sizes = torch.tensor([keep.numel() for keep in keeps], dtype=torch.int64, device=dev)
+    kcs = torch.tensor([f.n_clusters for f in layers], dtype=torch.int64, device=dev)
+    kept = torch.cat([keep.to(dev) for keep in keeps]) if keeps else torch.zeros(0, dtype=torch.int64, device=dev)
+    empty = row < 0
+    layer = layer_index.clamp(min=0)
+    if kept.numel():
+        original = kept[((sizes.cumsum(0) - sizes)[layer] + row).masked_fill(empty, 0)]
+    else:
+        original = torch.zeros_like(row)
+    kc = kcs[layer] if kcs.numel() else torch.ones_like(row)
+    component = torch.div(original, kc, rounding_mode="floor").masked_fill(empty, -1)
+    facet = (original % kc).masked_fill(empty, -1)
+    return vals, layer_index, component, facet, names
+
+
+# ------------------------------------------------------------------------------------------------
 # compare: two concept DBs against each other, both directions from one cosine pass (K6 tiles + K20, DESIGN.md §K20)
 # ------------------------------------------------------------------------------------------------
 @dataclass
@@ -474,6 +538,12 @@ class Lens:
     def search_components_image(self, query, aggregated_concept_db, k=10):
         return search_components_image(self.fm, query, aggregated_concept_db, k)
 
+    def label_facets(self, vocabulary, facets, k=5, templates=None, batch_size=None, chunk_size=None):
+        return label_facets(self.fm, vocabulary, facets, k, templates, batch_size, chunk_size)
+
+    def search_facets(self, query, facets, k=10, templates=None):
+        return search_facets(self.fm, query, facets, k, templates)
+
     def compare_concept_dbs(self, aggregated_concept_db_a, aggregated_concept_db_b, chunk_rows=None):
         return compare_concept_dbs(aggregated_concept_db_a, aggregated_concept_db_b, chunk_rows)
 
@@ -502,3 +572,7 @@ class Lens:
     def eval_polysemanticity(self, concept_db):
         """``polysemanticity_score`` of a ``(C, n, D)`` tensor or dict of tensors (lens.py:451-480)."""
         return self._per_layer(polysemanticity_score, concept_db)
+
+    def eval_facets(self, concept_db, n_clusters=2):
+        """``polysemanticity_facets`` of a ``(C, n, D)`` tensor or of each layer of a dict: a ``Facets`` or a dict of them."""
+        return self._per_layer(lambda V: polysemanticity_facets(V, n_clusters=n_clusters), concept_db)

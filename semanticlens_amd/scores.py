@@ -8,6 +8,7 @@ implementation behind these functions: without a HIP device they raise.
 from __future__ import annotations
 
 import logging
+from dataclasses import dataclass
 
 import numpy as np
 import torch
@@ -81,3 +82,71 @@ def polysemanticity_score(V, replace_empty_clusters=True, random_state=123, n_cl
     """
     first, rand = kmeans_draws(V.shape[-2], 10, random_state, n_clusters)
     return N.poly2means(V, first, rand, replace_empty_clusters, n_clusters=n_clusters).to(V.device)
+
+
+@dataclass
+class Facets:
+    """What ``polysemanticity_facets`` returns: the clustering each component's polysemanticity score comes from, split into
+    its ``kc = n_clusters`` facets.  Every tensor lives on the input's device.
+
+    * ``score (C,)`` float64: bit-equal to ``polysemanticity_score`` with the same arguments.
+    * ``labels (C, n)`` int32: scikit-learn's ``labels_`` (reference scores.py:167), aligned with the sample axis of
+      ``concept_db[layer]`` and so with ``ActMax.sample_ids``; facet ``j`` is the ``j``-th seeded centre.
+    * ``counts (C, kc)`` int32: facet sizes.
+    * ``centers (C, kc, D)`` float32: the mean embedding of a facet's samples — what ``concept_db.mean(1)`` is for the whole
+      component, and what the reference reads as ``cluster_centers_`` (scores.py:168).  Zeros for an empty facet.
+    * ``clarity (C, kc)`` float32: ``clarity_score`` within the facet; NaN for fewer than two samples."""
+
+    score: torch.Tensor
+    labels: torch.Tensor
+    counts: torch.Tensor
+    centers: torch.Tensor
+    clarity: torch.Tensor
+
+    @property
+    def n_clusters(self) -> int:
+        return int(self.centers.shape[1])
+
+    def aggregated(self) -> torch.Tensor:
+        """``(C * kc, D)``: row ``c * kc + j`` is facet ``j`` of component ``c`` — an aggregated concept DB of facets."""
+        return self.centers.reshape(-1, self.centers.shape[-1])
+
+    def members(self, j: int) -> torch.Tensor:
+        """``(C, n)`` bool: the samples of facet ``j``."""
+        if not 0 <= j < self.n_clusters:
+            raise IndexError(f"facet {j} not in [0, {self.n_clusters})")
+        return self.labels == j
+
+    def decode(self, rows: torch.Tensor):
+        """Rows of ``aggregated()`` -> ``(component, facet)`` = ``(row // kc, row % kc)``; a negative row (an empty slot) gives
+        ``(-1, -1)``."""
+        kc = self.n_clusters
+        empty = rows < 0
+        return (torch.div(rows, kc, rounding_mode="floor").masked_fill(empty, -1), (rows % kc).masked_fill(empty, -1))
+
+
+@torch.inference_mode()
+def polysemanticity_facets(V, n_clusters=2, random_state=123, replace_empty_clusters=True) -> Facets:
+    """``polysemanticity_score`` together with the clustering it scores: per component the ``n_clusters`` facets' labels,
+    sizes, mean embeddings and clarity (``Facets``).
+
+    Kernel K9 exports the ``labels_`` of the scikit-learn run it replays (reference scores.py:167-168); kernel K21 reduces
+    every facet's raw and normalised rows in one read of ``V``.  Same limits and ``ValueError``s as
+    ``polysemanticity_score``."""
+    if V.ndim != 3:
+        raise ValueError("polysemanticity_facets expects a (n_components, n_samples, n_features) tensor")
+    if n_clusters < 2:
+        raise ValueError(f"n_clusters={n_clusters} must be at least 2")
+    if n_clusters > N.POLYK_MAX_CLUSTERS:
+        raise ValueError(f"n_clusters={n_clusters} exceeds the device kernel's maximum of {N.POLYK_MAX_CLUSTERS}")
+    first, rand = kmeans_draws(V.shape[-2], 10, random_state, n_clusters)
+    Vd = N._f32c(V)
+    C, n, D = Vd.shape
+    dev = Vd.device
+    labels = torch.empty((C, n), dtype=torch.int32, device=dev)
+    centers = torch.empty((C, n_clusters, D), dtype=torch.float32, device=dev)
+    counts = torch.empty((C, n_clusters), dtype=torch.int32, device=dev)
+    clarity = torch.empty((C, n_clusters), dtype=torch.float32, device=dev)
+    score = N.poly2means(Vd, first, rand, replace_empty_clusters, n_clusters=n_clusters, labels=labels,
+                         stats=(centers, counts, clarity))
+    return Facets(*(t.to(V.device) for t in (score, labels, counts, centers, clarity)))
