@@ -517,6 +517,13 @@ int sl_mutualmax_merge(uint64_t* d_row_state, uint64_t* d_col_state, int64_t R, 
 /* Decode n state entries into K17's k = 1 form: d_vals (n,) fp32 and d_ids (n,) int64; an empty entry gives (-inf, -1). */
 int sl_mutualmax_finish(const uint64_t* d_state, int64_t n, float* d_vals, int64_t* d_ids, void* stream);
 
+/* K22: per-segment column maxima of a cosine tile (lens.audit_concepts).  State entry (g, j) is d_state[g * state_ld + j], j in [0, B);
+   packing, order and decoding are K20's (sl_mutualmax_finish decodes it).  Row r has the id row_id_base + r and belongs to segment
+   d_row_seg[r]; a row whose segment is outside [0, G) is ignored.  The rows of a segment need not be adjacent; runs of equal segments are
+   what makes it cheap. */
+int sl_segmax_merge(uint64_t* d_state, int64_t state_ld, int64_t G, int64_t R, int64_t B, const float* d_cand, int64_t ld,
+                    const int32_t* d_row_seg, int64_t row_id_base, void* stream);
+
 /* normalize(x) @ normalize(y)^T for ANY shapes — x (M,K), y (N,K), out (M,N) — with K6's kernels and arithmetic mode
  * (sl_set_gemm_mode) and none of similarity_score's shape branches: what the tiled top-k probing calls per tile.
  * d_ws: sl_cosine_nt_ws_bytes(M,N,K) bytes. */
@@ -533,7 +540,7 @@ size_t sl_cosine_nt_ws_bytes(int64_t M, int64_t N, int64_t K);
 #define SL_PROF_GATHER 3
 #define SL_PROF_SCORES 4
 #define SL_PROF_BATCHNORM 5 /* K16 fused inference BatchNorm; launches = BatchNorm2d evaluations (K19) */
-#define SL_PROF_TOPK 6 /* K17 streaming fp32 top-k; K20 mutual best matches */
+#define SL_PROF_TOPK 6 /* K17 streaming fp32 top-k; K20 mutual best matches; K22 per-segment maxima */
 #define SL_PROF_NFAM 7
 int sl_prof_enable(int on);
 int sl_prof_reset(void);

@@ -9,7 +9,8 @@ HIP device, compute calls raise.
 from __future__ import annotations
 
 from semanticlens_amd import foundation_models, scores, utils
-from semanticlens_amd.lens import ConceptDBComparison, Lens, compare_concept_dbs, label_facets, search_facets
+from semanticlens_amd.lens import (ConceptAudit, ConceptDBComparison, Lens, audit_concepts, compare_concept_dbs, label_facets,
+                                   probe_setmax, search_facets)
 from semanticlens_amd.scores import Facets, clarity_score, polysemanticity_facets, polysemanticity_score, redundancy_score
 
 __version__ = "0.1.0"
@@ -21,6 +22,9 @@ __all__ = [
     "Lens",
     "compare_concept_dbs",
     "ConceptDBComparison",
+    "audit_concepts",
+    "ConceptAudit",
+    "probe_setmax",
     "clarity_score",
     "polysemanticity_score",
     "redundancy_score",

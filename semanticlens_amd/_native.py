@@ -128,6 +128,7 @@ SIGNATURES = {
     "sl_topk_merge_states": (_int, [_vp, _vp, _i64, _i64, _vp, _vp, _i64, _vp]),
     "sl_mutualmax_merge": (_int, [_vp, _vp, _i64, _i64, _vp, _i64, _i64, _i64, _vp]),
     "sl_mutualmax_finish": (_int, [_vp, _i64, _vp, _vp, _vp]),
+    "sl_segmax_merge": (_int, [_vp, _i64, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _vp]),
     "sl_cosine_nt": (_int, [_vp, _i64, _vp, _i64, _i64, _vp, _vp, _sz, _vp]),
     "sl_cosine_nt_ws_bytes": (_sz, [_i64, _i64, _i64]),
     "sl_prof_enable": (_int, [_int]),
@@ -1015,6 +1016,108 @@ def mutual_probe(x: torch.Tensor, y: torch.Tensor, chunk_rows: int | None = None
                 cosine_nt(xd[r0 : r0 + nr], yd[c0 : c0 + nc], out, ws)
                 mutualmax_merge(row_state[r0 : r0 + nr], col_state[c0 : c0 + nc], out, r0, c0)
     return mutualmax_finish(row_state), mutualmax_finish(col_state)
+
+
+# ------------------------------------------------------------------------------------------------
+# K22: per-set best cosine (the column maxima of every cosine tile, one per segment of its rows)
+# ------------------------------------------------------------------------------------------------
+def segmax_merge(state: torch.Tensor, cand: torch.Tensor, row_seg: torch.Tensor, row_id_base: int = 0):
+    """Fold the ``(R, B)`` fp32 tile ``cand`` (unit column stride, any row stride) into ``state (G, B)``: entry ``(g, j)`` is the
+    best row of column ``j`` among the rows ``r`` with ``row_seg[r] == g`` (rows whose segment is outside ``[0, G)`` are
+    ignored).  ``state`` is an int64 device tensor of K20's packed entries with unit column stride and any row stride — a column
+    slice of a ``(G, C)`` state — and ``torch.zeros`` is the empty state; ``row_seg`` is ``(R,)`` int32 on the device; row ``r``
+    has the id ``row_id_base + r`` within ``[0, MUTUALMAX_MAX_ID]``."""
+    if cand.ndim != 2 or cand.dtype != torch.float32 or not cand.is_cuda:
+        raise ValueError(f"segmax_merge: the candidate tile must be a 2-D float32 device tensor, got {tuple(cand.shape)} {cand.dtype}")
+    R, B = cand.shape
+    if state.ndim != 2 or state.dtype != torch.int64 or state.device != cand.device or state.shape[1] != B:
+        raise ValueError(f"segmax_merge: the state must be a (G, {B}) int64 tensor on {cand.device}, got {tuple(state.shape)} "
+                         f"{state.dtype} on {state.device}")
+    G = state.shape[0]
+    state_ld = state.stride(0) if G > 1 else B
+    if (B > 1 and state.stride(1) != 1) or state_ld < B:
+        raise ValueError(f"segmax_merge: the state needs unit column stride and a row stride of at least {B}, got {state.stride()}")
+    if row_seg.ndim != 1 or row_seg.dtype != torch.int32 or row_seg.device != cand.device or row_seg.shape[0] != R:
+        raise ValueError(f"segmax_merge: the segment table must be a ({R},) int32 tensor on {cand.device}, got {tuple(row_seg.shape)} "
+                         f"{row_seg.dtype} on {row_seg.device}")
+    if R > 1 and row_seg.stride(0) != 1:
+        row_seg = row_seg.contiguous()
+    if B > 1 and cand.stride(1) != 1:
+        cand = cand.contiguous()
+    ld = cand.stride(0) if R > 1 else B
+    if ld < B:
+        cand, ld = cand.contiguous(), B
+    with _on(cand.device):
+        rc = lib().sl_segmax_merge(_ptr(state), state_ld, G, R, B, _ptr(cand), ld, _ptr(row_seg), row_id_base, _stream(cand))
+    _check(rc, "sl_segmax_merge")
+
+
+def check_set_offsets(set_offsets, P: int) -> list[int]:
+    """``G + 1`` host ints, non-decreasing, from 0 to ``P`` (a set may be empty); returns them as a list."""
+    try:
+        offsets = [operator.index(o) for o in set_offsets]
+    except TypeError:
+        raise ValueError(f"set_offsets must be a sequence of integers, got {set_offsets!r}") from None
+    if not offsets or offsets[0] != 0 or offsets[-1] != P:
+        raise ValueError(f"set_offsets must start at 0 and end at the number of prompt rows ({P}), got {offsets[:1]} ... {offsets[-1:]}")
+    if any(b < a for a, b in zip(offsets, offsets[1:])):
+        raise ValueError("set_offsets must be non-decreasing")
+    return offsets
+
+
+def setmax_probe(x: torch.Tensor, set_offsets, y: torch.Tensor, chunk_rows: int | None = None, chunk_cols: int | None = None,
+                 id_base: int = 0, state: torch.Tensor | None = None) -> torch.Tensor:
+    """Per set of prompt vectors and per row of ``y (C, D)``: the best cosine over the set and the prompt that has it, as the raw
+    ``(G, C)`` int64 state (decode with ``setmax_finish``; pass it back as ``state=`` with the next chunk of prompts, whose first
+    row has the id ``id_base``).  ``x (P, D)`` holds the prompt vectors set-major, set ``g`` being rows
+    ``set_offsets[g]:set_offsets[g + 1]``.  Order as in ``mutual_probe``: NaN first, then the larger cosine, equal cosines by
+    the smaller id.
+
+    Tiling is ``mutual_probe``'s: the cosine GEMM (K6, in the arithmetic ``set_gemm_mode`` selects) writes one reused tile of
+    ``chunk_rows`` prompts against ``chunk_cols`` rows of ``y`` and K22 folds its per-set column maxima into the state on the
+    same stream, so the ``(P, C)`` matrix never exists.  By default a tile spans all of ``y`` and as many prompts as keep it at
+    or under ``TOPK_TILE_BYTES``; ``y`` is cut too only where a single row of the tile would pass that size."""
+    if x.ndim != 2 or y.ndim != 2:
+        raise ValueError("setmax_probe expects 2-D tensors")
+    if y.shape[1] != x.shape[1]:
+        raise ValueError(f"embedding widths differ: {x.shape[1]} vs {y.shape[1]}")
+    for name, chunk in (("chunk_rows", chunk_rows), ("chunk_cols", chunk_cols)):
+        if chunk is not None and chunk < 1:
+            raise ValueError(f"{name} = {chunk} must be at least 1")
+    m, n = x.shape[0], y.shape[0]
+    offsets = check_set_offsets(set_offsets, m)
+    G = len(offsets) - 1
+    if id_base < 0 or id_base + m > MUTUALMAX_MAX_ID + 1:
+        raise ValueError(f"setmax_probe: prompt ids from {id_base} leave [0, {MUTUALMAX_MAX_ID}], the range a packed state entry holds")
+    if state is not None and (state.ndim != 2 or tuple(state.shape) != (G, n) or state.dtype != torch.int64 or not state.is_cuda):
+        raise ValueError(f"setmax_probe: state must be a ({G}, {n}) int64 device tensor, got {tuple(state.shape)} {state.dtype}")
+    xd = _f32c(x)
+    yd = _f32c(y, xd.device)
+    if state is None:
+        state = torch.zeros((G, n), dtype=torch.int64, device=xd.device)
+    if m and n and G:
+        counts = torch.tensor([b - a for a, b in zip(offsets, offsets[1:])], dtype=torch.int64)
+        seg = torch.repeat_interleave(torch.arange(G, dtype=torch.int32), counts).to(xd.device)
+        cols = min(chunk_cols or min(n, TOPK_TILE_BYTES // 4), n)
+        rows = min(chunk_rows or topk_chunk_rows(cols, m), m)  # rows of a (rows, cols) tile at or under the tile size
+        tile = torch.empty(rows * cols, dtype=torch.float32, device=xd.device)
+        ws = torch.empty(int(lib().sl_cosine_nt_ws_bytes(rows, cols, xd.shape[1])), dtype=torch.uint8, device=xd.device)
+        for r0 in range(0, m, rows):
+            nr = min(rows, m - r0)
+            for c0 in range(0, n, cols):
+                nc = min(cols, n - c0)
+                out = tile[: nr * nc].view(nr, nc)
+                cosine_nt(xd[r0 : r0 + nr], yd[c0 : c0 + nc], out, ws)
+                segmax_merge(state[:, c0 : c0 + nc], out, seg[r0 : r0 + nr], id_base + r0)
+    return state
+
+
+def setmax_finish(state: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
+    """Decode a ``(G, C)`` state: ``(values (G, C) float32, ids (G, C) int64)``, ``(-inf, -1)`` for a set that held no prompt."""
+    if state.ndim != 2:
+        raise ValueError(f"setmax_finish: a state is a (G, C) int64 device tensor, got {tuple(state.shape)}")
+    vals, ids = mutualmax_finish(state.contiguous().view(-1))
+    return vals.view(state.shape), ids.view(state.shape)
 
 
 # ------------------------------------------------------------------------------------------------

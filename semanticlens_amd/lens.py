@@ -10,6 +10,8 @@ from __future__ import annotations
 import os
 
 import logging
+import operator
+from collections.abc import Mapping
 from dataclasses import dataclass
 
 import torch
@@ -480,6 +482,169 @@ def compare_concept_dbs(aggregated_concept_db_a, aggregated_concept_db_b, chunk_
     )
 
 
+# ------------------------------------------------------------------------------------------------
+# audit: per-set best cosine of named text-concept sets, without the (prompts, components) matrix (K6 tiles + K22)
+# ------------------------------------------------------------------------------------------------
+@dataclass
+class ConceptAudit:
+    """What ``audit_concepts`` returns.  Every tensor lives on the DB's device (its layer's, for a dict DB).
+
+    * ``sets``: the set names; ``prompts``: all prompts, set-major; ``set_offsets``: ``G + 1`` offsets into ``prompts``.
+    * ``layers``: the layer names (``[None]`` for a tensor DB).
+    * ``alignment[layer]``: ``(G, C)`` float32, row ``g`` = every component's best cosine over set ``g``'s prompts;
+      ``best_prompt[layer]``: ``(G, C)`` int64, the index into ``prompts`` of the prompt that has it.
+
+    ``margin`` / ``flag`` / ``rank`` take set names (one or a list) for ``valid`` and ``spurious``; a NaN alignment (a NaN in an
+    embedding) propagates into the margin."""
+
+    sets: list
+    prompts: list
+    set_offsets: list
+    layers: list
+    alignment: dict
+    best_prompt: dict
+
+    def _rows(self, names) -> list[int]:
+        names = [names] if isinstance(names, str) or not isinstance(names, (list, tuple)) else list(names)
+        if not names:
+            raise ValueError("at least one set name is needed")
+        for name in names:
+            if name not in self.sets:
+                raise KeyError(name)
+        return [self.sets.index(name) for name in names]
+
+    def _best(self, layer, rows: list[int]) -> torch.Tensor:
+        return torch.amax(self.alignment[layer][rows], dim=0)
+
+    def margin(self, valid, spurious) -> dict:
+        """``{layer: (C,) float32}``: the best alignment over the ``spurious`` sets minus the best over the ``valid`` sets."""
+        v, s = self._rows(valid), self._rows(spurious)
+        return {layer: self._best(layer, s) - self._best(layer, v) for layer in self.layers}
+
+    def flag(self, valid, spurious, margin: float = 0.0, min_alignment: float | None = None) -> dict:
+        """``{layer: bool (C,)}``: ``margin(valid, spurious) > margin``, and with ``min_alignment`` also a spurious alignment of
+        at least that.  A NaN margin or alignment flags nothing (every comparison with a NaN is false)."""
+        v, s = self._rows(valid), self._rows(spurious)
+        out = {}
+        for layer in self.layers:
+            best_s = self._best(layer, s)
+            mask = (best_s - self._best(layer, v)) > margin
+            if min_alignment is not None:
+                mask &= best_s >= min_alignment
+            out[layer] = mask
+        return out
+
+    def rank(self, valid, spurious, k: int = 20, importance=None):
+        """The ``k`` components with the largest ``importance * margin`` across all layers: ``(values (k,), layer_index (k,),
+        component (k,))``.  ``importance``: a ``(C,)`` tensor (every layer) or a dict of them per layer — a classifier row for
+        the last layer, say; a layer missing from the dict counts as 1.  Order: NaN first, then the larger value, ties by the
+        earlier layer and then the smaller component; ``k`` beyond the number of components is clipped."""
+        k = operator.index(k)
+        if k < 1:
+            raise ValueError(f"k = {k} must be at least 1")
+        margins = self.margin(valid, spurious)
+        scores = []
+        for layer in self.layers:
+            m = margins[layer]
+            w = importance.get(layer) if isinstance(importance, dict) else importance
+            if w is not None:
+                w = torch.as_tensor(w)
+                if tuple(w.shape) != tuple(m.shape):
+                    raise ValueError(f"importance of layer {layer!r} has shape {tuple(w.shape)}, the layer has {m.shape[0]} components")
+                m = m * w.to(device=m.device, dtype=m.dtype)
+            scores.append(m)
+        dev = scores[0].device
+        flat = torch.cat([s.to(dev) for s in scores])
+        vals, order = torch.sort(flat, descending=True, stable=True)  # torch sorts NaN as the largest
+        k = min(k, flat.numel())
+        layer_index, component = _decode_layers(order[:k], [s.numel() for s in scores])
+        return vals[:k], layer_index, component
+
+    def describe(self, layer, component: int) -> list:
+        """``[(set name, alignment, prompt string)]`` of one component, in the order of ``sets`` (a host list)."""
+        vals = self.alignment[layer][:, component].tolist()
+        ids = self.best_prompt[layer][:, component].tolist()
+        return [(name, v, self.prompts[i] if i >= 0 else None) for name, v, i in zip(self.sets, vals, ids)]
+
+
+def _check_concept_sets(concept_sets):
+    """``(names, flat set-major prompts, G + 1 offsets)`` of a non-empty mapping of names to non-empty lists of strings."""
+    if not isinstance(concept_sets, Mapping) or len(concept_sets) == 0:
+        raise ValueError("concept_sets must be a non-empty mapping of set names to lists of prompts")
+    names, prompts, offsets = [], [], [0]
+    for name, members in concept_sets.items():
+        if isinstance(members, str) or not isinstance(members, (list, tuple)) or len(members) == 0:
+            raise ValueError(f"concept set {name!r} must be a non-empty list of strings")
+        for p in members:
+            if not isinstance(p, str):
+                raise ValueError(f"concept set {name!r} holds {p!r}, which is not a string")
+        names.append(name)
+        prompts.extend(members)
+        offsets.append(len(prompts))
+    return names, prompts, offsets
+
+
+@torch.no_grad()
+def probe_setmax(query_embeds: torch.Tensor, set_offsets, aggregated_concept_db, chunk_rows: int | None = None):
+    """Per set of query vectors and per component, the best cosine over the set and the query that has it, for callers who bring
+    their own vectors: ``(values (G, C) float32, ids (G, C) int64)`` with ``ids`` indexing ``query_embeds``, or a dict of such
+    pairs for a dict DB.  ``query_embeds (P, D)`` is set-major, set ``g`` being rows ``set_offsets[g]:set_offsets[g + 1]``; an
+    empty set holds ``-inf`` / ``-1``.  The ``(P, C)`` matrix is never formed (``_native.setmax_probe``: K6 tiles + K22).
+    Results live on the DB's device."""
+    names, layers, is_dict = _db_layers(aggregated_concept_db)
+    _check_width(query_embeds, layers)
+    N.check_set_offsets(set_offsets, query_embeds.shape[0])
+    out = {}
+    q = None
+    for name, layer in zip(names, layers):
+        ld = N._f32c(layer)
+        q = N._f32c(query_embeds, ld.device) if q is None or q.device != ld.device else q
+        vals, ids = N.setmax_finish(N.setmax_probe(q, set_offsets, ld, chunk_rows))
+        out[name] = (vals.to(layer.device), ids.to(layer.device))
+    return out if is_dict else out[None]
+
+
+@torch.no_grad()
+def audit_concepts(fm, concept_sets, aggregated_concept_db, templates: list[str] | None = None, batch_size: int | None = None,
+                   chunk_size: int | None = None) -> ConceptAudit:
+    """Audit a concept DB against named sets of text concepts — for a class, what the model should rely on ("valid") and what it
+    should not ("spurious"): for every component its alignment with each set (the best cosine over the set's prompts), the
+    prompt that gives it, and through ``ConceptAudit.margin`` / ``flag`` / ``rank`` the components that follow a spurious set
+    more than a valid one.
+
+    ``concept_sets`` is an ordered mapping ``{set name: [prompt, ...]}``.  The prompts are embedded ``chunk_size`` at a time
+    (default ``LABEL_CHUNK_WORDS``; ``batch_size`` is the text tower's batch) with ``label_components``' template convention —
+    each prompt's mean over ITS OWN templates minus the empty-template embedding — and each chunk is folded into every layer's
+    ``(G, C)`` state (``_native.setmax_probe``) before the next is embedded; a set may straddle chunks.  Neither the
+    ``(prompts, components)`` matrix nor, for ``chunk_size`` below the prompt count, all embeddings are ever resident.  A prompt
+    that occurs in two sets is embedded twice.
+
+    The sets, ``chunk_size`` and the DB's shape are checked before anything runs; as in ``label_components`` a ``D`` mismatch
+    raises ``ValueError`` only after the first chunk has been embedded."""
+    sets, prompts, offsets = _check_concept_sets(concept_sets)
+    if chunk_size is not None and chunk_size < 1:
+        raise ValueError(f"chunk_size = {chunk_size} must be at least 1")
+    names, layers, _ = _db_layers(aggregated_concept_db)
+    dbs = [N._f32c(layer) for layer in layers]  # raises without a HIP device, before the text tower runs
+    states = [None] * len(dbs)
+    step = chunk_size or LABEL_CHUNK_WORDS
+    empty = None
+    if templates:
+        empty = fm.encode_text(fm.tokenize([t.format("") for t in templates]).to(fm.device))
+    for start in range(0, len(prompts), step):
+        stop = min(start + step, len(prompts))
+        embeds = _embed_words(fm, prompts[start:stop], templates, batch_size, empty)
+        _check_width(embeds, layers)
+        local = [min(max(o, start), stop) - start for o in offsets]  # the chunk's slice of every set (most are empty)
+        for i, db in enumerate(dbs):
+            states[i] = N.setmax_probe(embeds.to(db.device), local, db, id_base=start, state=states[i])
+    alignment, best_prompt = {}, {}
+    for name, layer, state in zip(names, layers, states):
+        vals, ids = N.setmax_finish(state)
+        alignment[name], best_prompt[name] = vals.to(layer.device), ids.to(layer.device)
+    return ConceptAudit(sets=sets, prompts=prompts, set_offsets=offsets, layers=names, alignment=alignment, best_prompt=best_prompt)
+
+
 class Lens:
     """Holds the foundation model and wraps the workflow (reference: lens.py:217-480)."""
 
@@ -546,6 +711,9 @@ class Lens:
 
     def compare_concept_dbs(self, aggregated_concept_db_a, aggregated_concept_db_b, chunk_rows=None):
         return compare_concept_dbs(aggregated_concept_db_a, aggregated_concept_db_b, chunk_rows)
+
+    def audit_concepts(self, concept_sets, aggregated_concept_db, templates=None, batch_size=None, chunk_size=None):
+        return audit_concepts(self.fm, concept_sets, aggregated_concept_db, templates, batch_size, chunk_size)
 
     @staticmethod
     def _per_layer(fn, db):
