@@ -303,6 +303,23 @@ int sl_polykmeans_labels(const float* d_V, int64_t C, int64_t n, int64_t D, int 
 int sl_facet_stats(const float* d_V, int64_t C, int64_t n, int64_t D, const int32_t* d_labels, int n_clusters,
                    float* d_centres, int32_t* d_counts, float* d_clarity, void* stream);
 
+/* ---- K23: silhouette — how many facets a component has (scikit-learn's silhouette_samples / silhouette_score) -----------
+ * V (C,n,D) fp32, labels (m,C,n) int32: m label sets over the same samples (the candidate clusterings k = 2..K of
+ * polysemanticity_facets(n_clusters="auto")) -> samples (m,C,n) fp64 (may be NULL), mean (m,C) fp64.
+ *   cnt_j = #{l: label_l = j};  S_i(j) = sum over l != i with label_l = j of d(i,l)   (l == i is skipped by index)
+ *   i in cluster A:  a = S_i(A) / (cnt_A - 1),  b = min over non-empty j != A of S_i(j) / cnt_j,  s_i = (b - a) / max(a, b);
+ *   s_i = 0 when cnt_A == 1 or max(a, b) == 0;  mean = mean of s_i over the samples that are in.
+ * A label outside [0,n_clusters) takes the sample out, as in sl_facet_stats: it enters no sum, its s_i is NaN, the mean
+ * skips it.  Fewer than two non-empty clusters (scikit-learn raises): every s_i and the mean are NaN.
+ * metric 0, euclidean: d(i,l) = sqrt(max(H_ii + H_ll - 2 H_il, 0));
+ * metric 1, cosine:    d(i,l) = 1 - H_il / (max(sqrt(H_ii), 1e-12) * max(sqrt(H_ll), 1e-12));
+ * H = V_c V_c^T accumulated in fp64 from exact fp32 products, (C,n,n) in the workspace: V is read once per call, not once
+ * per label set.  1 <= m <= 15, 2 <= n_clusters <= 16, 2 <= n <= 1024, any D >= 1, C <= 65535 per call (C == 0: no-op).
+ * All sums are fp64 in a fixed order; results depend on neither the grid nor m; no float atomics. */
+size_t sl_silhouette_ws_bytes(int64_t C, int64_t n, int64_t D);
+int sl_silhouette(const float* d_V, int64_t C, int64_t n, int64_t D, const int32_t* d_labels, int m, int n_clusters, int metric,
+                  double* d_samples, double* d_mean, void* d_ws, size_t ws_bytes, void* stream);
+
 /* ---- K10: template-difference mean of text embeddings (lens.py:196-199) ------------------
  * E (Q*T,D) read as "(q t) d", E0 (T,D); out (Q,D) = mean_t(E[q,t] - E0[t]). */
 int sl_template_mean(const float* d_E, const float* d_E0, int64_t Q, int64_t T, int64_t D, float* d_out,

@@ -11,7 +11,8 @@ from __future__ import annotations
 from semanticlens_amd import foundation_models, scores, utils
 from semanticlens_amd.lens import (ConceptAudit, ConceptDBComparison, Lens, audit_concepts, compare_concept_dbs, label_facets,
                                    probe_setmax, search_facets)
-from semanticlens_amd.scores import Facets, clarity_score, polysemanticity_facets, polysemanticity_score, redundancy_score
+from semanticlens_amd.scores import (Facets, clarity_score, polysemanticity_facets, polysemanticity_score, redundancy_score,
+                                     silhouette_samples, silhouette_score)
 
 __version__ = "0.1.0"
 
@@ -32,4 +33,6 @@ __all__ = [
     "polysemanticity_facets",
     "label_facets",
     "search_facets",
+    "silhouette_samples",
+    "silhouette_score",
 ]

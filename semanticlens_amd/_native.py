@@ -93,6 +93,8 @@ SIGNATURES = {
     "sl_poly2means_labels": (_int, [_vp, _i64, _i64, _i64, _vp, _int, _vp, _int, _vp, _vp, _vp, _vp, _sz, _vp]),
     "sl_polykmeans_labels": (_int, [_vp, _i64, _i64, _i64, _int, _vp, _int, _vp, _int, _vp, _vp, _vp, _vp, _sz, _vp]),
     "sl_facet_stats": (_int, [_vp, _i64, _i64, _i64, _vp, _int, _vp, _vp, _vp, _vp]),
+    "sl_silhouette_ws_bytes": (_sz, [_i64, _i64, _i64]),
+    "sl_silhouette": (_int, [_vp, _i64, _i64, _i64, _vp, _int, _int, _int, _vp, _vp, _vp, _sz, _vp]),
     "sl_linear": (_int, [_vp, _i64, _i64, _vp, _i64, _vp, _int, _vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp]),
     "sl_layernorm": (_int, [_vp, _i64, _i64, _i64, _vp, _vp, ctypes.c_float, _vp, _vp, _i64, _vp]),
     "sl_attention": (_int, [_vp, _i64, _i64, _i64, _i64, _int, _vp, _vp, _vp]),
@@ -1269,6 +1271,74 @@ def facet_stats(V: torch.Tensor, labels: torch.Tensor, n_clusters: int, clarity:
         if clar is not None:
             clar.fill_(float("nan"))
     return centres, counts, clar
+
+
+SIL_MAX_N = 1024        # sl_silhouette: samples per component (kSilMaxN in csrc/silhouette.hip)
+SIL_MAX_CLUSTERS = 16   # sl_silhouette: n_clusters (kSilMaxClusters)
+SIL_MAX_SETS = 15       # sl_silhouette: label sets per call (kSilMaxSets)
+SIL_METRICS = {"euclidean": 0, "cosine": 1}
+
+
+def check_silhouette_metric(metric) -> int:
+    """``metric`` as ``sl_silhouette``'s code; ``ValueError`` for anything but ``"euclidean"`` and ``"cosine"``."""
+    if not isinstance(metric, str) or metric not in SIL_METRICS:
+        raise ValueError(f"metric={metric!r} is not one of {sorted(SIL_METRICS)}")
+    return SIL_METRICS[metric]
+
+
+def silhouette(V: torch.Tensor, labels: torch.Tensor, n_clusters: int, metric: str = "euclidean", samples: bool = True):
+    """K23: scikit-learn's ``silhouette_samples`` / ``silhouette_score`` of every component of ``V (C, n, D)`` under ``labels
+    (C, n)`` or ``(m, C, n)`` int32 (``m`` label sets, one read of ``V``): ``(samples float64 shaped like labels, or None; mean
+    float64 (C,) or (m, C))``, on the device.  A label outside ``[0, n_clusters)`` takes the sample out (NaN, not part of the
+    mean); fewer than two non-empty clusters give NaN.
+
+    Any number of components: calls are chunked by the Gram kernel's grid limit (65 535 components) and by the workspace
+    budget K9 uses — every component is independent, so the results do not change."""
+    if V.ndim != 3 or labels.ndim not in (2, 3) or tuple(labels.shape[-2:]) != tuple(V.shape[:2]):
+        raise ValueError(f"silhouette expects V (C, n, D) and labels (C, n) or (m, C, n), got {tuple(V.shape)} and {tuple(labels.shape)}")
+    if labels.dtype != torch.int32:
+        raise ValueError(f"labels must be int32, got {labels.dtype}")
+    C, n, D = V.shape
+    m = labels.shape[0] if labels.ndim == 3 else 1
+    if not 1 <= m <= SIL_MAX_SETS:
+        raise ValueError(f"m={m} label sets not in [1, {SIL_MAX_SETS}]")
+    if isinstance(n_clusters, bool) or not isinstance(n_clusters, int) or not 2 <= n_clusters <= SIL_MAX_CLUSTERS:
+        raise ValueError(f"n_clusters={n_clusters!r} not in [2, {SIL_MAX_CLUSTERS}]")
+    if not 2 <= n <= SIL_MAX_N:
+        raise ValueError(f"n_samples={n} not in [2, {SIL_MAX_N}]: the device kernel's range of samples per component")
+    if D < 1:
+        raise ValueError(f"D={D}: at least one feature")
+    code = check_silhouette_metric(metric)
+    Vd = _f32c(V)
+    ld = to_device(labels, Vd.device).contiguous().view(m, C, n)
+    dev = Vd.device
+    out_s = torch.empty((m, C, n), dtype=torch.float64, device=dev) if samples else None
+    out_m = torch.empty((m, C), dtype=torch.float64, device=dev)
+    if C:
+        per_comp = n * n * 8
+        chunk = max(1, min(C, POLYK_MAX_COMPONENTS, _poly_ws_budget() // per_comp))
+        ws = None
+        with _on(dev):
+            for c0 in range(0, C, chunk):
+                cc = min(chunk, C - c0)
+                whole = cc == C
+                # a chunk of the (m, C, ...) tensors is not contiguous: it goes through contiguous copies
+                lc = ld if whole else ld[:, c0:c0 + cc].contiguous()
+                sc = out_s if whole or out_s is None else torch.empty((m, cc, n), dtype=torch.float64, device=dev)
+                mc = out_m if whole else torch.empty((m, cc), dtype=torch.float64, device=dev)
+                nbytes = int(lib().sl_silhouette_ws_bytes(cc, n, D))
+                if ws is None:
+                    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+                rc = lib().sl_silhouette(_ptr(Vd[c0:c0 + cc]), cc, n, D, _ptr(lc), m, n_clusters, code, _ptr(sc), _ptr(mc), _ptr(ws),
+                                         nbytes, _stream(Vd))
+                _check(rc, "sl_silhouette")
+                if not whole:
+                    out_m[:, c0:c0 + cc] = mc
+                    if out_s is not None:
+                        out_s[:, c0:c0 + cc] = sc
+    if labels.ndim == 2:
+        return (out_s[0] if out_s is not None else None), out_m[0]
+    return out_s, out_m
 
 
 def poly2means(V: torch.Tensor, first_center, rand, replace_empty_clusters: bool = True, n_clusters: int = 2, labels=None,

@@ -24,69 +24,14 @@
 // the two scikit-learn takes hangs on the rounding of its BLAS distances (tools/k9_postmortem.py; ~1 in 1 500 components
 // of tiny random inputs ends in another clustering for it: profiles/r05_k9_near_tie.txt).
 #include "common.hpp"
+#include "gram.hpp"
 
 namespace sl {
 namespace {
 
-constexpr int kMaxN = 128;
+constexpr int kMaxN = kGramStagedMaxN;
 
-// ---- launch 1: H[c] = V_c V_c^T (fp64 accumulation of exact fp32 products) ----------------------
-// One workgroup per component; the (n x Dc) slab is staged in LDS (rows padded by one float) and each
-// thread owns pairs p = t, t + 256, ... of the upper triangle.
-__global__ __launch_bounds__(256) void gram_kernel(const float* __restrict__ V, int64_t C, int n, int64_t D, int Dc,
-                                                    double* __restrict__ H) {
-  extern __shared__ float s_v[];  // n x (Dc + 1)
-  const int ld = Dc + 1;
-  const int npairs = n * (n + 1) / 2;
-  constexpr int kMaxPairsPerThread = (kMaxN * (kMaxN + 1) / 2 + 255) / 256;
-  for (int64_t c = blockIdx.x; c < C; c += gridDim.x) {
-    const float* Vc = V + c * (int64_t)n * D;
-    double acc[kMaxPairsPerThread];
-#pragma unroll
-    for (int a = 0; a < kMaxPairsPerThread; ++a) acc[a] = 0.0;
-    for (int64_t d0 = 0; d0 < D; d0 += Dc) {
-      const int dc = (int)((D - d0) < Dc ? (D - d0) : Dc);
-      __syncthreads();
-      for (int e = threadIdx.x; e < n * dc; e += 256) {
-        const int i = e / dc, d = e % dc;
-        s_v[i * ld + d] = Vc[(int64_t)i * D + d0 + d];
-      }
-      __syncthreads();
-#pragma unroll
-      for (int a = 0; a < kMaxPairsPerThread; ++a) {
-        const int p = threadIdx.x + a * 256;
-        if (p < npairs) {
-          // p -> (i, j), i <= j, row-major upper triangle
-          int i = 0, rem = p;
-          while (rem >= n - i) {
-            rem -= n - i;
-            ++i;
-          }
-          const int j = i + rem;
-          const float* a_ = s_v + i * ld;
-          const float* b_ = s_v + j * ld;
-          double s = 0.0;
-          for (int d = 0; d < dc; ++d) s += (double)a_[d] * (double)b_[d];
-          acc[a] += s;
-        }
-      }
-    }
-#pragma unroll
-    for (int a = 0; a < kMaxPairsPerThread; ++a) {
-      const int p = threadIdx.x + a * 256;
-      if (p < npairs) {
-        int i = 0, rem = p;
-        while (rem >= n - i) {
-          rem -= n - i;
-          ++i;
-        }
-        const int j = i + rem;
-        H[(c * n + i) * n + j] = acc[a];
-        H[(c * n + j) * n + i] = acc[a];
-      }
-    }
-  }
-}
+// ---- launch 1: H[c] = V_c V_c^T (fp64 accumulation of exact fp32 products): gram_kernel / gram_general_kernel, gram.hpp ----
 
 // ---- launch 2: KMeans(2) per component, one wave per component ------------------------------------
 struct Draws {
@@ -786,25 +731,6 @@ __global__ __launch_bounds__(64) void kmeansk_kernel(const double* __restrict__ 
     }
     out[c] = poly;
     if (min_count) min_count[c] = mc;
-  }
-}
-
-// Gram matrices for any n (the staged kernel above keeps a register array sized for n <= 128): one thread per pair,
-// rows read from L2.  H[c] = V_c V_c^T in fp64.
-__global__ __launch_bounds__(256) void gram_general_kernel(const float* __restrict__ V, int64_t C, int n, int64_t D,
-                                                            double* __restrict__ H) {
-  const int64_t c = blockIdx.y;
-  const int64_t npairs = (int64_t)n * n;
-  const float* Vc = V + c * (int64_t)n * D;
-  for (int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x; p < npairs; p += (int64_t)gridDim.x * 256) {
-    const int i = (int)(p / n), j = (int)(p % n);
-    if (j < i) continue;
-    const float* a = Vc + (int64_t)i * D;
-    const float* b = Vc + (int64_t)j * D;
-    double s = 0.0;
-    for (int64_t d = 0; d < D; ++d) s += (double)a[d] * (double)b[d];
-    H[(c * n + i) * n + j] = s;
-    H[(c * n + j) * n + i] = s;
   }
 }
 

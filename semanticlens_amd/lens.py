@@ -741,6 +741,7 @@ class Lens:
         """``polysemanticity_score`` of a ``(C, n, D)`` tensor or dict of tensors (lens.py:451-480)."""
         return self._per_layer(polysemanticity_score, concept_db)
 
-    def eval_facets(self, concept_db, n_clusters=2):
-        """``polysemanticity_facets`` of a ``(C, n, D)`` tensor or of each layer of a dict: a ``Facets`` or a dict of them."""
-        return self._per_layer(lambda V: polysemanticity_facets(V, n_clusters=n_clusters), concept_db)
+    def eval_facets(self, concept_db, n_clusters=2, **kwargs):
+        """``polysemanticity_facets`` of a ``(C, n, D)`` tensor or of each layer of a dict: a ``Facets`` or a dict of them.
+        ``n_clusters="auto"`` and the keywords (``max_clusters``, ``min_silhouette``, ``metric``, ...) are forwarded."""
+        return self._per_layer(lambda V: polysemanticity_facets(V, n_clusters=n_clusters, **kwargs), concept_db)

@@ -95,13 +95,24 @@ class Facets:
     * ``counts (C, kc)`` int32: facet sizes.
     * ``centers (C, kc, D)`` float32: the mean embedding of a facet's samples — what ``concept_db.mean(1)`` is for the whole
       component, and what the reference reads as ``cluster_centers_`` (scores.py:168).  Zeros for an empty facet.
-    * ``clarity (C, kc)`` float32: ``clarity_score`` within the facet; NaN for fewer than two samples."""
+    * ``clarity (C, kc)`` float32: ``clarity_score`` within the facet; NaN for fewer than two samples.
+
+    With ``n_clusters="auto"`` (kernel K23) every component has its own number of facets, ``kc = max_clusters`` is the fixed
+    width of the tensors above and the facets a component does not use are empty (count 0, zero centre, NaN clarity), which
+    ``label_facets`` and ``search_facets`` skip.  Two more fields, ``None`` after a fixed-``n_clusters`` call:
+
+    * ``n_facets (C,)`` int32: the chosen facet count, 1 for a component without substantial cluster structure; ``score`` is
+      the polysemanticity at that count, 0.0 where it is 1.
+    * ``silhouette (C, max_clusters - 1)`` float64: column ``k - 2`` is the mean silhouette of the ``k``-facet clustering;
+      NaN for a ``k`` that was not tried (``k >= n``) or whose clustering has fewer than two non-empty clusters."""
 
     score: torch.Tensor
     labels: torch.Tensor
     counts: torch.Tensor
     centers: torch.Tensor
     clarity: torch.Tensor
+    n_facets: torch.Tensor | None = None
+    silhouette: torch.Tensor | None = None
 
     @property
     def n_clusters(self) -> int:
@@ -126,15 +137,41 @@ class Facets:
 
 
 @torch.inference_mode()
-def polysemanticity_facets(V, n_clusters=2, random_state=123, replace_empty_clusters=True) -> Facets:
+def silhouette_samples(V, labels, metric="euclidean"):
+    """scikit-learn's ``silhouette_samples`` for every component: ``V (C, n, D)``, ``labels (C, n)`` or ``(m, C, n)`` int32 ->
+    float64 shaped like ``labels``.  Labels are cluster ids in ``[0, 16)``; any other value (``-1``) takes the sample out: its
+    value is NaN and it enters nobody's distances.  Fewer than two non-empty clusters give NaN.  Kernel K23."""
+    return N.silhouette(V, labels, N.SIL_MAX_CLUSTERS, metric)[0].to(V.device)
+
+
+@torch.inference_mode()
+def silhouette_score(V, labels, metric="euclidean"):
+    """scikit-learn's ``silhouette_score`` for every component: the mean of ``silhouette_samples`` over the samples that are in,
+    float64 ``(C,)`` or ``(m, C)``; NaN where fewer than two clusters are non-empty.  Kernel K23."""
+    return N.silhouette(V, labels, N.SIL_MAX_CLUSTERS, metric, samples=False)[1].to(V.device)
+
+
+@torch.inference_mode()
+def polysemanticity_facets(V, n_clusters=2, random_state=123, replace_empty_clusters=True, max_clusters=6, min_silhouette=0.25,
+                           metric="euclidean") -> Facets:
     """``polysemanticity_score`` together with the clustering it scores: per component the ``n_clusters`` facets' labels,
     sizes, mean embeddings and clarity (``Facets``).
 
     Kernel K9 exports the ``labels_`` of the scikit-learn run it replays (reference scores.py:167-168); kernel K21 reduces
     every facet's raw and normalised rows in one read of ``V``.  Same limits and ``ValueError``s as
-    ``polysemanticity_score``."""
+    ``polysemanticity_score``.
+
+    ``n_clusters="auto"`` chooses every component's facet count: the ``k`` in ``2..min(max_clusters, n - 1)`` whose clustering
+    has the largest mean silhouette (kernel K23, ``metric`` "euclidean" or "cosine"; ties go to the smaller ``k``) if that
+    silhouette reaches ``min_silhouette``, otherwise one facet (0.25 is Kaufman and Rousseeuw's "no substantial structure"
+    line).  The tensors then have ``max_clusters`` facet slots, see ``Facets``.  ``max_clusters``, ``min_silhouette`` and
+    ``metric`` are read only then."""
     if V.ndim != 3:
         raise ValueError("polysemanticity_facets expects a (n_components, n_samples, n_features) tensor")
+    if isinstance(n_clusters, str):
+        if n_clusters != "auto":
+            raise ValueError(f"n_clusters={n_clusters!r}: an integer or \"auto\"")
+        return _facets_auto(V, max_clusters, min_silhouette, metric, random_state, replace_empty_clusters)
     if n_clusters < 2:
         raise ValueError(f"n_clusters={n_clusters} must be at least 2")
     if n_clusters > N.POLYK_MAX_CLUSTERS:
@@ -150,3 +187,36 @@ def polysemanticity_facets(V, n_clusters=2, random_state=123, replace_empty_clus
     score = N.poly2means(Vd, first, rand, replace_empty_clusters, n_clusters=n_clusters, labels=labels,
                          stats=(centers, counts, clarity))
     return Facets(*(t.to(V.device) for t in (score, labels, counts, centers, clarity)))
+
+
+def _facets_auto(V, max_clusters, min_silhouette, metric, random_state, replace_empty_clusters) -> Facets:
+    """``polysemanticity_facets(V, "auto")``: K9 once per candidate ``k``, one K23 call over the stacked labels, the selection in
+    torch on the device, one K21 call at ``kc = max_clusters``."""
+    n = V.shape[1]
+    if isinstance(max_clusters, bool) or not isinstance(max_clusters, int) or not 2 <= max_clusters <= N.SIL_MAX_CLUSTERS:
+        raise ValueError(f"max_clusters={max_clusters!r} not in [2, {N.SIL_MAX_CLUSTERS}]")
+    if n < 3:
+        raise ValueError(f"n_samples={n}: choosing a facet count needs at least 3 samples per component (candidates k = 2..n - 1)")
+    N.check_silhouette_metric(metric)
+    K = min(max_clusters, n - 1)
+    Vd = N._f32c(V)
+    C, n, D = Vd.shape
+    dev = Vd.device
+    labels = torch.empty((K - 1, C, n), dtype=torch.int32, device=dev)
+    score = torch.empty((K - 1, C), dtype=torch.float64, device=dev)
+    for k in range(2, K + 1):
+        first, rand = kmeans_draws(n, 10, random_state, k)
+        score[k - 2] = N.poly2means(Vd, first, rand, replace_empty_clusters, n_clusters=k, labels=labels[k - 2])
+    sil = N.silhouette(Vd, labels, K, metric, samples=False)[1]  # (K - 1, C)
+    key = sil.masked_fill(sil.isnan(), float("-inf"))
+    top = key.max(0).values
+    ks = torch.arange(K - 1, device=dev)[:, None]
+    best = torch.where(key == top, ks, K - 1).min(0).values  # the smallest k among the best
+    single = ~(top >= min_silhouette)
+    n_facets = (best + 2).masked_fill(single, 1).to(torch.int32)
+    chosen = labels.gather(0, best[None, :, None].expand(1, C, n))[0].masked_fill(single[:, None], 0)
+    chosen_score = score.gather(0, best[None])[0].masked_fill(single, 0.0)
+    centers, counts, clarity = N.facet_stats(Vd, chosen, max_clusters)
+    silhouette = torch.full((C, max_clusters - 1), float("nan"), dtype=torch.float64, device=dev)
+    silhouette[:, :K - 1] = sil.T
+    return Facets(*(t.to(V.device) for t in (chosen_score, chosen, counts, centers, clarity, n_facets, silhouette)))
