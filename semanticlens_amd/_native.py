@@ -850,6 +850,17 @@ def topk_new(R: int, k: int, device) -> tuple[torch.Tensor, torch.Tensor]:
     return vals, ids
 
 
+def _tile_view(cand: torch.Tensor) -> tuple[torch.Tensor, int]:
+    """``(cand, ld)`` as the merge kernels read an ``(R, B)`` tile: unit column stride, a row stride of at least ``B``, else a copy."""
+    R, B = cand.shape
+    if B > 1 and cand.stride(1) != 1:
+        cand = cand.contiguous()
+    ld = cand.stride(0) if R > 1 else B
+    if ld < B:
+        cand, ld = cand.contiguous(), B
+    return cand, ld
+
+
 def topk_merge(vals: torch.Tensor, ids: torch.Tensor, cand: torch.Tensor, id_base: int = 0, ws: torch.Tensor | None = None):
     """Fold the ``(R, B)`` fp32 tile ``cand`` (unit column stride, any row stride) into the state; column ``j`` has the id
     ``id_base + j``.  ``ws``: a uint8 device buffer to use as the workspace of a split row when it is large enough."""
@@ -857,11 +868,7 @@ def topk_merge(vals: torch.Tensor, ids: torch.Tensor, cand: torch.Tensor, id_bas
     if cand.ndim != 2 or cand.shape[0] != R or cand.dtype != torch.float32 or not cand.is_cuda:
         raise ValueError(f"topk_merge: candidate tile {tuple(cand.shape)} {cand.dtype} does not fit a state of {R} rows")
     B = cand.shape[1]
-    if B > 1 and cand.stride(1) != 1:
-        cand = cand.contiguous()
-    ld = cand.stride(0) if R > 1 else B
-    if ld < B:
-        cand, ld = cand.contiguous(), B
+    cand, ld = _tile_view(cand)
     nbytes = int(lib().sl_topk_merge_ws_bytes(R, k, B))
     if nbytes and (ws is None or ws.numel() < nbytes):
         ws = torch.empty(nbytes, dtype=torch.uint8, device=vals.device)
@@ -901,6 +908,47 @@ def topk_chunk_rows(R: int, n_cols: int, tile_bytes: int = TOPK_TILE_BYTES) -> i
     return max(1, min(n_cols, tile_bytes // (4 * max(R, 1))))
 
 
+def _check_probe_args(fn: str, x: torch.Tensor, y: torch.Tensor, **chunks):
+    """What every probe checks first, before a device is touched: 2-D operands of one width, ``chunk_*`` of at least 1."""
+    if x.ndim != 2 or y.ndim != 2:
+        raise ValueError(f"{fn} expects 2-D tensors")
+    if y.shape[1] != x.shape[1]:
+        raise ValueError(f"embedding widths differ: {x.shape[1]} vs {y.shape[1]}")
+    for name, chunk in chunks.items():
+        if chunk is not None and chunk < 1:
+            raise ValueError(f"{name} = {chunk} must be at least 1")
+
+
+def tile_plan(m: int, n: int, chunk_rows: int | None = None, chunk_cols: int | None = None) -> tuple[int, int]:
+    """``(rows, cols)`` of ``mutual_probe``'s / ``setmax_probe``'s tile of an ``(m, n)`` cosine matrix: by default all ``n`` columns and
+    as many rows as keep it at or under ``TOPK_TILE_BYTES``; the columns are cut too only where a single row would pass that size."""
+    cols = min(chunk_cols or min(n, TOPK_TILE_BYTES // 4), n)
+    return min(chunk_rows or topk_chunk_rows(cols, m), m), cols
+
+
+def tile_walk(m: int, n: int, rows: int, cols: int):
+    """The ``(r0, nr, c0, nc)`` rectangles of ``(rows, cols)`` tiles over an ``(m, n)`` matrix, row blocks outermost."""
+    for r0 in range(0, m, rows):
+        for c0 in range(0, n, cols):
+            yield r0, min(rows, m - r0), c0, min(cols, n - c0)
+
+
+def _cosine_tiles(xd: torch.Tensor, yd: torch.Tensor, rows: int, cols: int):
+    """``normalize(xd) @ normalize(yd).T`` one ``tile_walk`` rectangle at a time, as ``(r0, nr, c0, nc, out)``: the cosine GEMM (K6)
+    writes ``out (nr, nc)`` into ONE reused buffer, with one reused workspace (both allocated by the call, before anything is
+    iterated), on the operands' stream; the consumer folds it on that stream before asking for the next."""
+    tile = torch.empty(rows * cols, dtype=torch.float32, device=xd.device)
+    ws = torch.empty(int(lib().sl_cosine_nt_ws_bytes(rows, cols, xd.shape[1])), dtype=torch.uint8, device=xd.device)
+
+    def tiles():
+        for r0, nr, c0, nc in tile_walk(xd.shape[0], yd.shape[0], rows, cols):
+            out = tile[: nr * nc].view(nr, nc)
+            cosine_nt(xd[r0 : r0 + nr], yd[c0 : c0 + nc], out, ws)
+            yield r0, nr, c0, nc, out
+
+    return tiles()
+
+
 def topk_probe(x: torch.Tensor, y: torch.Tensor, k: int, chunk_rows: int | None = None, id_base: int = 0, state=None):
     """Per row of ``x (R, D)``: the ``k`` largest cosines against the rows of ``y (N, D)`` (row ``j`` has the id
     ``id_base + j``), as ``(values (R, k) float32, ids (R, k) int64)``.
@@ -909,36 +957,27 @@ def topk_probe(x: torch.Tensor, y: torch.Tensor, k: int, chunk_rows: int | None 
     the arithmetic ``set_gemm_mode`` selects) writes one reused ``(R, chunk_rows)`` tile at a time and K17 folds it into the
     state on the same stream, so the ``(R, N)`` matrix never exists.  ``state``: continue an existing ``(values, ids)`` pair."""
     k = check_topk_k(k)
-    if x.ndim != 2 or y.ndim != 2:
-        raise ValueError("topk_probe expects 2-D tensors")
-    if y.shape[1] != x.shape[1]:
-        raise ValueError(f"embedding widths differ: {x.shape[1]} vs {y.shape[1]}")
-    if chunk_rows is not None and chunk_rows < 1:
-        raise ValueError(f"chunk_rows = {chunk_rows} must be at least 1")
+    _check_probe_args("topk_probe", x, y, chunk_rows=chunk_rows)
     xd = _f32c(x)
     yd = _f32c(y, xd.device)
     R, n = xd.shape[0], yd.shape[0]
     vals, ids = state if state is not None else topk_new(R, k, xd.device)
     if R == 0 or n == 0:
         return vals, ids
-    step = min(chunk_rows or topk_chunk_rows(R, n), n)
-    tile = torch.empty(R * step, dtype=torch.float32, device=xd.device)
-    ws = torch.empty(int(lib().sl_cosine_nt_ws_bytes(R, step, xd.shape[1])), dtype=torch.uint8, device=xd.device)
+    step = min(chunk_rows or topk_chunk_rows(R, n), n)  # a tile spans all of x: the walk's single-row-block case
+    tiles = _cosine_tiles(xd, yd, R, step)
     # the split-row workspace is largest for the widest tile (the waves per row grow with the columns), so one buffer serves all
     merge_bytes = int(lib().sl_topk_merge_ws_bytes(R, k, step))
     merge_ws = torch.empty(merge_bytes, dtype=torch.uint8, device=xd.device) if merge_bytes else None
-    for start in range(0, n, step):
-        rows = min(step, n - start)
-        out = tile[: R * rows].view(R, rows)
-        cosine_nt(xd, yd[start : start + rows], out, ws)
-        topk_merge(vals, ids, out, id_base + start, merge_ws)
+    for _, _, c0, _, out in tiles:
+        topk_merge(vals, ids, out, id_base + c0, merge_ws)
     return vals, ids
 
 
 # ------------------------------------------------------------------------------------------------
 # K20: mutual best matches (row and column maxima of every cosine tile in one read)
 # ------------------------------------------------------------------------------------------------
-MUTUALMAX_MAX_ID = (1 << 32) - 2  # a packed state entry holds a 32-bit id; 2^32 - 1 is left out
+MUTUALMAX_MAX_ID = (1 << 32) - 2  # a packed state entry holds a 32-bit id; 2^32 - 1 is left out (csrc/packed_best.hpp: kMaxPackedId)
 
 
 def _check_mutualmax_state(what: str, state: torch.Tensor, n: int | None = None):
@@ -959,11 +998,7 @@ def mutualmax_merge(row_state: torch.Tensor, col_state: torch.Tensor, cand: torc
     R, B = cand.shape
     _check_mutualmax_state("mutualmax_merge", row_state, R)
     _check_mutualmax_state("mutualmax_merge", col_state, B)
-    if B > 1 and cand.stride(1) != 1:
-        cand = cand.contiguous()
-    ld = cand.stride(0) if R > 1 else B
-    if ld < B:
-        cand, ld = cand.contiguous(), B
+    cand, ld = _tile_view(cand)
     with _on(cand.device):
         rc = lib().sl_mutualmax_merge(_ptr(row_state), _ptr(col_state), R, B, _ptr(cand), ld, row_id_base, col_id_base, _stream(cand))
     _check(rc, "sl_mutualmax_merge")
@@ -989,15 +1024,8 @@ def mutual_probe(x: torch.Tensor, y: torch.Tensor, chunk_rows: int | None = None
 
     The cosine GEMM (K6, in the arithmetic ``set_gemm_mode`` selects) writes one reused tile of ``chunk_rows`` rows of ``x``
     against ``chunk_cols`` rows of ``y`` and K20 folds its row and column maxima into two states on the same stream; the
-    ``(len(x), len(y))`` matrix never exists.  By default a tile spans all of ``y`` and as many rows of ``x`` as keep it at or
-    under ``TOPK_TILE_BYTES``; ``y`` is cut too only where a single row of the tile would pass that size."""
-    if x.ndim != 2 or y.ndim != 2:
-        raise ValueError("mutual_probe expects 2-D tensors")
-    if y.shape[1] != x.shape[1]:
-        raise ValueError(f"embedding widths differ: {x.shape[1]} vs {y.shape[1]}")
-    for name, chunk in (("chunk_rows", chunk_rows), ("chunk_cols", chunk_cols)):
-        if chunk is not None and chunk < 1:
-            raise ValueError(f"{name} = {chunk} must be at least 1")
+    ``(len(x), len(y))`` matrix never exists.  ``tile_plan`` has the default tile."""
+    _check_probe_args("mutual_probe", x, y, chunk_rows=chunk_rows, chunk_cols=chunk_cols)
     if max(x.shape[0], y.shape[0]) > MUTUALMAX_MAX_ID + 1:
         raise ValueError(f"mutual_probe: more than {MUTUALMAX_MAX_ID + 1} rows do not fit a packed state's 32-bit ids")
     xd = _f32c(x)
@@ -1006,17 +1034,8 @@ def mutual_probe(x: torch.Tensor, y: torch.Tensor, chunk_rows: int | None = None
     row_state = torch.zeros(m, dtype=torch.int64, device=xd.device)
     col_state = torch.zeros(n, dtype=torch.int64, device=xd.device)
     if m and n:
-        cols = min(chunk_cols or min(n, TOPK_TILE_BYTES // 4), n)
-        rows = min(chunk_rows or topk_chunk_rows(cols, m), m)  # rows of a (rows, cols) tile at or under the tile size
-        tile = torch.empty(rows * cols, dtype=torch.float32, device=xd.device)
-        ws = torch.empty(int(lib().sl_cosine_nt_ws_bytes(rows, cols, xd.shape[1])), dtype=torch.uint8, device=xd.device)
-        for r0 in range(0, m, rows):
-            nr = min(rows, m - r0)
-            for c0 in range(0, n, cols):
-                nc = min(cols, n - c0)
-                out = tile[: nr * nc].view(nr, nc)
-                cosine_nt(xd[r0 : r0 + nr], yd[c0 : c0 + nc], out, ws)
-                mutualmax_merge(row_state[r0 : r0 + nr], col_state[c0 : c0 + nc], out, r0, c0)
+        for r0, nr, c0, nc, out in _cosine_tiles(xd, yd, *tile_plan(m, n, chunk_rows, chunk_cols)):
+            mutualmax_merge(row_state[r0 : r0 + nr], col_state[c0 : c0 + nc], out, r0, c0)
     return mutualmax_finish(row_state), mutualmax_finish(col_state)
 
 
@@ -1044,11 +1063,7 @@ def segmax_merge(state: torch.Tensor, cand: torch.Tensor, row_seg: torch.Tensor,
                          f"{row_seg.dtype} on {row_seg.device}")
     if R > 1 and row_seg.stride(0) != 1:
         row_seg = row_seg.contiguous()
-    if B > 1 and cand.stride(1) != 1:
-        cand = cand.contiguous()
-    ld = cand.stride(0) if R > 1 else B
-    if ld < B:
-        cand, ld = cand.contiguous(), B
+    cand, ld = _tile_view(cand)
     with _on(cand.device):
         rc = lib().sl_segmax_merge(_ptr(state), state_ld, G, R, B, _ptr(cand), ld, _ptr(row_seg), row_id_base, _stream(cand))
     _check(rc, "sl_segmax_merge")
@@ -1077,15 +1092,8 @@ def setmax_probe(x: torch.Tensor, set_offsets, y: torch.Tensor, chunk_rows: int 
 
     Tiling is ``mutual_probe``'s: the cosine GEMM (K6, in the arithmetic ``set_gemm_mode`` selects) writes one reused tile of
     ``chunk_rows`` prompts against ``chunk_cols`` rows of ``y`` and K22 folds its per-set column maxima into the state on the
-    same stream, so the ``(P, C)`` matrix never exists.  By default a tile spans all of ``y`` and as many prompts as keep it at
-    or under ``TOPK_TILE_BYTES``; ``y`` is cut too only where a single row of the tile would pass that size."""
-    if x.ndim != 2 or y.ndim != 2:
-        raise ValueError("setmax_probe expects 2-D tensors")
-    if y.shape[1] != x.shape[1]:
-        raise ValueError(f"embedding widths differ: {x.shape[1]} vs {y.shape[1]}")
-    for name, chunk in (("chunk_rows", chunk_rows), ("chunk_cols", chunk_cols)):
-        if chunk is not None and chunk < 1:
-            raise ValueError(f"{name} = {chunk} must be at least 1")
+    same stream, so the ``(P, C)`` matrix never exists."""
+    _check_probe_args("setmax_probe", x, y, chunk_rows=chunk_rows, chunk_cols=chunk_cols)
     m, n = x.shape[0], y.shape[0]
     offsets = check_set_offsets(set_offsets, m)
     G = len(offsets) - 1
@@ -1100,17 +1108,8 @@ def setmax_probe(x: torch.Tensor, set_offsets, y: torch.Tensor, chunk_rows: int 
     if m and n and G:
         counts = torch.tensor([b - a for a, b in zip(offsets, offsets[1:])], dtype=torch.int64)
         seg = torch.repeat_interleave(torch.arange(G, dtype=torch.int32), counts).to(xd.device)
-        cols = min(chunk_cols or min(n, TOPK_TILE_BYTES // 4), n)
-        rows = min(chunk_rows or topk_chunk_rows(cols, m), m)  # rows of a (rows, cols) tile at or under the tile size
-        tile = torch.empty(rows * cols, dtype=torch.float32, device=xd.device)
-        ws = torch.empty(int(lib().sl_cosine_nt_ws_bytes(rows, cols, xd.shape[1])), dtype=torch.uint8, device=xd.device)
-        for r0 in range(0, m, rows):
-            nr = min(rows, m - r0)
-            for c0 in range(0, n, cols):
-                nc = min(cols, n - c0)
-                out = tile[: nr * nc].view(nr, nc)
-                cosine_nt(xd[r0 : r0 + nr], yd[c0 : c0 + nc], out, ws)
-                segmax_merge(state[:, c0 : c0 + nc], out, seg[r0 : r0 + nr], id_base + r0)
+        for r0, nr, c0, nc, out in _cosine_tiles(xd, yd, *tile_plan(m, n, chunk_rows, chunk_cols)):
+            segmax_merge(state[:, c0 : c0 + nc], out, seg[r0 : r0 + nr], id_base + r0)
     return state
 
 

@@ -64,6 +64,12 @@ inline int num_cus() {
   return n;
 }
 
+// grid of a 256-thread grid-stride kernel over n > 0 items: at most eight blocks per CU
+inline unsigned stride_grid_256(int64_t n) {
+  const int64_t blocks = (n + 255) / 256, cap = (int64_t)num_cus() * 8;
+  return (unsigned)(blocks < cap ? blocks : cap);
+}
+
 // ---- bf16 / ordering helpers (device + host) ----------------------------------------------
 __host__ __device__ inline uint32_t f32_bits(float f) {
   union {
@@ -100,16 +106,7 @@ __host__ __device__ inline uint32_t bf16_order_key(uint16_t h) {
   return (h & 0x8000u) ? (0x8000u - mag) : (0x8000u + mag);
 }
 
-// monotone 32-bit key of an fp32: larger key == ranks earlier.  NaN -> all ones, -0.0 -> +0.0's key; every real value's key
-// is >= 0x007FFFFF (-inf), so 0 is free for the empty slot (K17's slots, K20's packed states)
-__device__ inline uint32_t f32_order_key(float v) {
-  const uint32_t u = f32_bits(v);
-  if ((u & 0x7FFFFFFFu) > 0x7F800000u) return 0xFFFFFFFFu;
-  if (u == 0x80000000u) return 0x80000000u;
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
-// total order: key desc, then id asc
+// total order: key (packed_best.hpp: f32_order_key) desc, then id asc
 __host__ __device__ inline bool better(uint32_t ka, int64_t ia, uint32_t kb, int64_t ib) {
   return ka > kb || (ka == kb && ia < ib);
 }

@@ -18,7 +18,7 @@
 // Few rows (search: a handful of queries against tens of thousands of components): the columns are split over S waves per
 // row, each of which selects its segment's top k into a workspace (filtered by the state's k-th entry: what that rejects
 // cannot reach the result), and a second launch folds the S lists into the state with the explicit-id kernel.
-#include "common.hpp"
+#include "colmax_tile.hpp"  // f4; f32_order_key through packed_best.hpp
 
 namespace sl {
 namespace {
@@ -28,9 +28,7 @@ constexpr int64_t kMaxId = (int64_t)1 << 62;
 constexpr int kMinBuf = 128;          // room behind the state: at least two appends of 64
 constexpr int64_t kMinSegment = 1024;  // columns per wave when a row is split
 
-typedef float f4 __attribute__((ext_vector_type(4)));
-
-// f32_order_key (common.hpp) of a slot; the empty slot's key is 0, below every real value's
+// f32_order_key (packed_best.hpp) of a slot; the empty slot's key is 0, below every real value's
 __device__ inline uint32_t entry_key(float v, int64_t id) { return id < 0 ? 0u : f32_order_key(v); }
 
 // One wavefront's selection state in LDS.  Every member function is called by all 64 lanes together.
@@ -111,7 +109,8 @@ struct WaveTopK {
   }
 };
 
-__device__ inline int pow2_entries(int k) {
+// LDS entries of a wave: the state and at least kMinBuf behind it (k <= kMaxK on both sides)
+__host__ __device__ inline int pow2_entries(int k) {
   int n = 256;
   while (n < k + kMinBuf) n <<= 1;
   return n;
@@ -226,12 +225,7 @@ __global__ __launch_bounds__(256) void topk_init_kernel(float* __restrict__ vals
   }
 }
 
-int host_pow2_entries(int64_t k) {
-  int n = 256;
-  while (n < k + kMinBuf) n <<= 1;
-  return n;
-}
-size_t lds_bytes(int64_t k) { return (size_t)host_pow2_entries(k) * 12; }
+size_t lds_bytes(int64_t k) { return (size_t)pow2_entries((int)k) * 12; }
 
 // waves per row: enough to give every CU eight waves, each with at least kMinSegment columns
 int64_t splits(int64_t R, int64_t B) {
@@ -266,10 +260,7 @@ SL_API int sl_topk_init(float* d_vals, int64_t* d_ids, int64_t R, int64_t k, voi
   if (R == 0) return 0;
   SL_REQUIRE(d_vals && d_ids, "sl_topk_init: null state");
   const int64_t n = R * k;
-  int64_t blocks = (n + 255) / 256;
-  const int64_t cap = (int64_t)num_cus() * 8;
-  if (blocks > cap) blocks = cap;
-  hipLaunchKernelGGL(topk_init_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, d_vals, d_ids, n);
+  hipLaunchKernelGGL(topk_init_kernel, dim3(stride_grid_256(n)), dim3(256), 0, (hipStream_t)stream, d_vals, d_ids, n);
   SL_CHECK_HIP(hipGetLastError());
   return 0;
 }

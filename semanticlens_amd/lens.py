@@ -184,6 +184,34 @@ def _embed_words(fm, words: list[str], templates: list[str] | None, batch_size: 
     return N.template_mean(templated, empty, len(words))
 
 
+def _embedded_chunks(fm, texts: list[str], layers, templates: list[str] | None, batch_size: int | None, chunk_size: int | None):
+    """``(start, stop, embeds)`` for ``texts`` embedded ``chunk_size`` (default ``LABEL_CHUNK_WORDS``) at a time, each chunk checked against
+    the DB's width.  The call checks ``chunk_size``; the text tower (empty templates first) only runs when the result is iterated."""
+    if chunk_size is not None and chunk_size < 1:
+        raise ValueError(f"chunk_size = {chunk_size} must be at least 1")
+    step = chunk_size or LABEL_CHUNK_WORDS
+    def chunks():
+        empty = fm.encode_text(fm.tokenize([t.format("") for t in templates]).to(fm.device)) if templates else None
+        for start in range(0, len(texts), step):
+            stop = min(start + step, len(texts))
+            embeds = _embed_words(fm, texts[start:stop], templates, batch_size, empty)
+            _check_width(embeds, layers)
+            yield start, stop, embeds
+
+    return chunks()
+
+
+def _probe_layers(names, layers, is_dict, query_embeds: torch.Tensor, probe):
+    """``probe(layer, queries) -> (values, ids)`` per layer, both operands on the layer's device as contiguous fp32 (the queries
+    move only when the device changes); results on the device the layer came from, a dict of them for a dict DB."""
+    out, q = {}, None
+    for name, layer in zip(names, layers):
+        ld = N._f32c(layer)
+        q = N._f32c(query_embeds, ld.device) if q is None or q.device != ld.device else q
+        out[name] = tuple(t.to(layer.device) for t in probe(ld, q))
+    return out if is_dict else out[None]
+
+
 def _decode_layers(ids: torch.Tensor, sizes: list[int]):
     """Global component ids (``offset[layer] + component``; -1 = empty slot) -> ``(layer_index, component)``."""
     ends = torch.tensor(sizes, dtype=torch.int64, device=ids.device).cumsum(0)
@@ -214,14 +242,7 @@ def probe_topk(query_embeds: torch.Tensor, aggregated_concept_db, k: int, per: s
     names, layers, is_dict = _db_layers(aggregated_concept_db)
     _check_width(query_embeds, layers)
     if per == "component":
-        out = {}
-        q = None
-        for name, layer in zip(names, layers):
-            ld = N._f32c(layer)
-            q = N._f32c(query_embeds, ld.device) if q is None or q.device != ld.device else q
-            vals, ids = N.topk_probe(ld, q, k, chunk_rows)
-            out[name] = (vals.to(layer.device), ids.to(layer.device))
-        return out if is_dict else out[None]
+        return _probe_layers(names, layers, is_dict, query_embeds, lambda ld, q: N.topk_probe(ld, q, k, chunk_rows))
     q = N._f32c(query_embeds)
     vals, ids = N.topk_new(q.shape[0], k, q.device)
     offset = 0
@@ -256,19 +277,11 @@ def label_components(fm, vocabulary: list[str], aggregated_concept_db, k: int = 
     k = N.check_topk_k(k)
     if isinstance(vocabulary, str) or not isinstance(vocabulary, (list, tuple)) or len(vocabulary) == 0:
         raise ValueError("vocabulary must be a non-empty list of strings")
-    if chunk_size is not None and chunk_size < 1:
-        raise ValueError(f"chunk_size = {chunk_size} must be at least 1")
     names, layers, is_dict = _db_layers(aggregated_concept_db)
-    vocabulary = list(vocabulary)
+    chunks = _embedded_chunks(fm, list(vocabulary), layers, templates, batch_size, chunk_size)
     dbs = [N._f32c(layer) for layer in layers]  # raises without a HIP device, before the text tower runs
     states = [None] * len(dbs)
-    step = chunk_size or LABEL_CHUNK_WORDS
-    empty = None
-    if templates:
-        empty = fm.encode_text(fm.tokenize([t.format("") for t in templates]).to(fm.device))
-    for start in range(0, len(vocabulary), step):
-        embeds = _embed_words(fm, vocabulary[start : start + step], templates, batch_size, empty)
-        _check_width(embeds, layers)
+    for start, _, embeds in chunks:
         for i, db in enumerate(dbs):
             states[i] = N.topk_probe(db, embeds, k, id_base=start, state=states[i])
     out = {name: (vals.to(layer.device), ids.to(layer.device)) for name, layer, (vals, ids) in zip(names, layers, states)}
@@ -594,14 +607,8 @@ def probe_setmax(query_embeds: torch.Tensor, set_offsets, aggregated_concept_db,
     names, layers, is_dict = _db_layers(aggregated_concept_db)
     _check_width(query_embeds, layers)
     N.check_set_offsets(set_offsets, query_embeds.shape[0])
-    out = {}
-    q = None
-    for name, layer in zip(names, layers):
-        ld = N._f32c(layer)
-        q = N._f32c(query_embeds, ld.device) if q is None or q.device != ld.device else q
-        vals, ids = N.setmax_finish(N.setmax_probe(q, set_offsets, ld, chunk_rows))
-        out[name] = (vals.to(layer.device), ids.to(layer.device))
-    return out if is_dict else out[None]
+    probe = lambda ld, q: N.setmax_finish(N.setmax_probe(q, set_offsets, ld, chunk_rows))  # noqa: E731
+    return _probe_layers(names, layers, is_dict, query_embeds, probe)
 
 
 @torch.no_grad()
@@ -622,19 +629,11 @@ def audit_concepts(fm, concept_sets, aggregated_concept_db, templates: list[str]
     The sets, ``chunk_size`` and the DB's shape are checked before anything runs; as in ``label_components`` a ``D`` mismatch
     raises ``ValueError`` only after the first chunk has been embedded."""
     sets, prompts, offsets = _check_concept_sets(concept_sets)
-    if chunk_size is not None and chunk_size < 1:
-        raise ValueError(f"chunk_size = {chunk_size} must be at least 1")
     names, layers, _ = _db_layers(aggregated_concept_db)
+    chunks = _embedded_chunks(fm, prompts, layers, templates, batch_size, chunk_size)
     dbs = [N._f32c(layer) for layer in layers]  # raises without a HIP device, before the text tower runs
     states = [None] * len(dbs)
-    step = chunk_size or LABEL_CHUNK_WORDS
-    empty = None
-    if templates:
-        empty = fm.encode_text(fm.tokenize([t.format("") for t in templates]).to(fm.device))
-    for start in range(0, len(prompts), step):
-        stop = min(start + step, len(prompts))
-        embeds = _embed_words(fm, prompts[start:stop], templates, batch_size, empty)
-        _check_width(embeds, layers)
+    for start, stop, embeds in chunks:
         local = [min(max(o, start), stop) - start for o in offsets]  # the chunk's slice of every set (most are empty)
         for i, db in enumerate(dbs):
             states[i] = N.setmax_probe(embeds.to(db.device), local, db, id_base=start, state=states[i])

@@ -888,6 +888,62 @@ def test_gemm_choice_header_on_the_host(tmp_path):
     assert "failures=0" in res.stdout
 
 
+def test_packed_best_header_on_the_host(tmp_path):
+    """csrc/packed_best.hpp compiled for the host: the fp32 order key against the documented order, its inverse, the packed
+    (value, id) entry's round trip and combine rule, and the id range (tests/native/packed_best_check.cpp holds the table)."""
+    exe = tmp_path / "packed_best_check"
+    subprocess.run(["g++", "-O2", "-std=c++17", "-Wall", "-Wextra", "-o", str(exe),
+                    str(ROOT / "tests" / "native" / "packed_best_check.cpp")], check=True)
+    res = subprocess.run([str(exe)], capture_output=True, text=True)
+    assert res.returncode == 0, res.stdout + res.stderr
+    assert "failures=0" in res.stdout
+
+
+# (m, n, chunk_rows, chunk_cols) -> the (rows, cols) of the tile, from the probes' expressions before `tile_plan` existed:
+# cols = min(chunk_cols or min(n, TOPK_TILE_BYTES // 4), n), rows = min(chunk_rows or topk_chunk_rows(cols, m), m)
+TILE_PLANS = {
+    (1, 1, None, None): (1, 1),
+    (5, 3, 2, 2): (2, 2),
+    (512, 4097, 129, 1500): (129, 1500),
+    (40000, 98304, None, None): (341, 98304),
+    (3, (128 << 20) // 4 + 5, None, None): (1, (128 << 20) // 4),
+}
+
+
+def _assert_partition(tiles, m, n):
+    """The (r0, nr, c0, nc) rectangles are the product of a partition of [0, m) and one of [0, n): they cover m x n exactly once."""
+    row_cuts = sorted({(r0, nr) for r0, nr, _, _ in tiles})
+    col_cuts = sorted({(c0, nc) for _, _, c0, nc in tiles})
+    for cuts, size in ((row_cuts, m), (col_cuts, n)):
+        assert cuts[0][0] == 0 and cuts[-1][0] + cuts[-1][1] == size
+        assert all(length >= 1 for _, length in cuts)
+        assert all(a + la == b for (a, la), (b, _) in zip(cuts, cuts[1:]))
+    assert len(tiles) == len(set(tiles)) == len(row_cuts) * len(col_cuts)
+    assert sum(nr * nc for _, nr, _, nc in tiles) == m * n
+
+
+@pytest.mark.parametrize("shape", list(TILE_PLANS), ids=lambda s: "x".join(str(v) for v in s))
+def test_tile_plan_and_walk_partition_the_matrix_within_the_byte_limit(shape):
+    """`_native.tile_plan` / `tile_walk`, the plan and walk under `mutual_probe`, `setmax_probe` and `topk_probe`, without a
+    device: default plans are the recorded ones, the rectangles partition m x n, every tile is at or under TOPK_TILE_BYTES, and
+    `topk_probe`'s plan is the walk with a single row block."""
+    m, n, chunk_rows, chunk_cols = shape
+    assert N.TOPK_TILE_BYTES == 128 << 20
+    rows, cols = N.tile_plan(m, n, chunk_rows, chunk_cols)
+    assert (rows, cols) == TILE_PLANS[shape]
+    tiles = list(N.tile_walk(m, n, rows, cols))
+    _assert_partition(tiles, m, n)
+    assert all(nr <= rows and nc <= cols for _, nr, _, nc in tiles) and rows * cols * 4 <= N.TOPK_TILE_BYTES
+    assert tiles == sorted(tiles)  # row blocks outermost, both ascending: the order the states' tests were recorded in
+    # topk_probe(x (m, D), y (n, D), chunk_rows=chunk_cols): the tile spans all of x and cuts y
+    step = min(chunk_cols or N.topk_chunk_rows(m, n), n)
+    topk_tiles = list(N.tile_walk(m, n, m, step))
+    _assert_partition(topk_tiles, m, n)
+    assert all((r0, nr) == (0, m) for r0, nr, _, _ in topk_tiles)
+    assert [c0 for _, _, c0, _ in topk_tiles] == list(range(0, n, step))
+    assert m * step * 4 <= N.TOPK_TILE_BYTES
+
+
 # ---- the aten tie order's host self-test (VERDICT r05 #12): restatement vs the installed torch.topk, no device -----------------------
 def test_aten_order_restatement_equals_the_installed_torch_topk():
     """`sl_aten_topk_order_host` is host code: the positions the K3 kernels' restatement selects against `torch.topk` on the CPU of
