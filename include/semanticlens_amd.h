@@ -75,7 +75,9 @@ int sl_abi_version(void);
 /* Variant switches — which of several BIT-IDENTICAL kernel variants a dispatcher picks (0 = its own rule).  The parity tests walk the
  * variants with these; production code never needs them.  Names: "g3_tile" (split-bf16 GEMM tile: 128, 256, 8, 160, 64, 1280),
  * "f32_tile" (fp32-MFMA GEMM: 128, 8), "g3_strip_off" (1: no column-strip split), "colreduce_nw" (K2 waves per task: 4, 8, 16),
- * "bn_policy" (K16 cache policy: 1 plain, 2 non-temporal stores, 3 non-temporal loads and stores; 0: 3 from 206 MB, else 1).
+ * "bn_policy" (K16 cache policy: 1 plain, 2 non-temporal stores, 3 non-temporal loads and stores; 0: 3 from 206 MB, else 1),
+ * "g3_shared" (split-bf16 GEMM tile rule: 1 by makespan on an empty chip, 2 by chip time as for a launch that shares the GPU with
+ * another stream; 0: by chip time on any stream but the device's default stream).
  * The environment variable SL_OPTIONS="name=value,..." presets them for a process; an explicit call wins.  No reference counterpart. */
 int sl_set_option(const char* name, int64_t value);
 int64_t sl_get_option(const char* name); /* -1 for an unknown name */

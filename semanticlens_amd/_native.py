@@ -469,7 +469,7 @@ def actmax_merge(vals, ids, cand: torch.Tensor, slot_stride: int, id_bases: list
 
 
 def set_option(name: str, value: int) -> None:
-    """Force one of several bit-identical kernel variants (``g3_tile``, ``f32_tile``, ``g3_strip_off``, ``colreduce_nw``, ``bn_policy``; 0 = the
+    """Force one of several bit-identical kernel variants (``g3_tile``, ``f32_tile``, ``g3_strip_off``, ``colreduce_nw``, ``bn_policy``, ``g3_shared``; 0 = the
     dispatcher's own rule).  For the parity tests; ``SL_OPTIONS="name=value,..."`` presets them for a process."""
     _check(lib().sl_set_option(name.encode(), int(value)), "sl_set_option")
 

@@ -347,7 +347,16 @@ using gemm_choice::G3Kernel;
 using gemm_choice::G3Part;
 
 // A (M rows), B (N rows): split matrices of K columns (layout above).  The kernel is gemm_choice.hpp's rule on this device and the
-// options of this dispatch: "g3_tile" (sl_set_option; tests) forces a kernel, "g3_strip_off" = 1 switches the column-strip cut off.
+// options of this dispatch: "g3_tile" (sl_set_option; tests) forces a kernel, "g3_strip_off" = 1 switches the column-strip cut off,
+// "g3_shared" says whether the launch shares the chip with another stream (gemm_choice.hpp: chip time instead of makespan).
+// g3_shared = 0: a launch on any stream but the device's default (null) stream counts as sharing: the package and the benchmark
+// put the embed on a side stream exactly when they run it beside the probed model's forward, and a standalone encode, text
+// probing and the cosine GEMM run on the default stream.  1: never (makespan rule), 2: always (chip-time rule).
+inline bool shares_chip(hipStream_t st) {
+  const int64_t o = option(OPT_G3_SHARED);
+  return o == 2 || (o != 1 && st != nullptr);
+}
+
 template <class Epi>
 int launch_gemm3_nt(ProfScope& prof, const uint16_t* A, int64_t M, const uint16_t* B, int64_t N, int64_t K, const Epi& epi,
                     hipStream_t st, G3Part part = G3Part::Whole) {
@@ -356,7 +365,7 @@ int launch_gemm3_nt(ProfScope& prof, const uint16_t* A, int64_t M, const uint16_
   if (tm * tn == 0) return 0;
   const int64_t Kp = split_kp(K);
   const bool strip_off = option(OPT_G3_STRIP_OFF) != 0;
-  const auto c = gemm_choice::choose_g3(M, N, Kp, num_cus(), (int)option(OPT_G3_TILE), strip_off, part);
+  const auto c = gemm_choice::choose_g3(M, N, Kp, num_cus(), (int)option(OPT_G3_TILE), strip_off, part, shares_chip(st));
   if (c.cut > 0) {  // columns [0, cut), then the strip: the same A, B rows from `cut` on, the epilogue shifted by `cut` columns
     if (int rc = launch_gemm3_nt(prof, A, M, B, c.cut, K, epi, st, G3Part::Main)) return rc;
     ProfScope strip(SL_PROF_GEMM, st, 0.0);  // its time counts, its flops are in `prof`'s work already

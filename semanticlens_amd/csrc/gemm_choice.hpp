@@ -1,6 +1,7 @@
 // Which MFMA GEMM kernel a shape gets: the size rules of the split-bf16 launcher (choose_g3, for gemm_bf16x3.hpp) and of the fp32
 // launcher (choose_f32, for gemm_f32.hpp) as pure functions of the shape, the CU count and the option values.
-// Needs only <cstdint>: a host compiler can include it (tests/native/gemm_choice_check.cpp holds the table).
+// Needs only <cstdint>: a host compiler can include it (tests/native/gemm_choice_check.cpp holds the table, and
+// tests/native/gemm_choice_shared_check.cpp the one of choose_g3's two rules side by side).
 // Every kernel of a family gives the same bits (tests/test_gpu_parity.py); the rules below only decide speed.
 #pragma once
 #include <cstdint>
@@ -84,6 +85,42 @@ inline int64_t strip_split_columns(int64_t M, int64_t N, int64_t cus, bool strip
   return best_m * 256;
 }
 
+// ---- a launch that shares the chip (option g3_shared) ------------------------------------------------------------------------
+// Every rule above prices a launch by its makespan on an otherwise empty chip.  A big-tile workgroup owns its CU (the 8-phase kernel
+// takes the whole register file, the 160 x 256 kernel the whole LDS), so when another stream has work queued the two streams take
+// turns on whole CUs: CUs a launch leaves idle run the other stream, and what the launch costs the step is its CHIP TIME, workgroups
+// x time per workgroup.  Per-workgroup times in units of one 256 x 256 tile of the 8-phase kernel, measured on the ViT-B/32 block
+// shapes at M = 12 800 with no other stream (tools/enc_gemm_lab.py 12800, SL_OPTIONS=g3_tile= 8 / 160 / 1280;
+// profiles/k11_shared_gemm_ratios.txt), us, bare epilogue / the block's own epilogue:
+//   160 x 256 tile (0.625 of the work), one round of 240 items against one round of 150 tiles:
+//     o-proj (K = 768) 43.4 / 51.9 against 51.3 / 60.2 = 0.85 / 0.86;  fc2 (K = 3072) 135.1 / 141.8 against 158.3 / 167.7 = 0.85 / 0.85
+//   128 x 128 ring tile (0.25 of the work), one workgroup per CU:
+//     fc1 2 400 tiles = 10 rounds in 210.6 against 600 tiles = 3 rounds in 161.5: 21.1 against 53.8 = 0.39
+//     o-proj 600 tiles = 3 rounds in 65.0 against one round in 51.3: 21.7 against 51.3 = 0.42
+// So 160-row tiles only pay where the rows quantise to as many items as tiles (M <= 160, or 256 < M <= 320), and a cut only where the
+// strip is at most 128 columns wide (2 x 0.40 per row tile against 1).
+constexpr double kW4TileTime = 0.85;
+constexpr double kRing128TileTime = 0.40;
+inline bool w4_prefer_shared(int64_t M, int64_t N, int64_t cus) {
+  const int64_t t256 = tiles_of(M, N), t160 = ((M + 159) / 160) * ((N + 255) / 256);
+  if (t256 * 2 < cus) return false;  // small grids: as w4_prefer
+  return (double)t160 * kW4TileTime < (double)t256;
+}
+// the column at which to cut, 0 = no cut: the candidates of strip_split_columns, priced in tiles instead of rounds
+inline int64_t strip_split_columns_shared(int64_t M, int64_t N, bool strip_off) {
+  const int64_t tm = (M + 255) / 256, tn = (N + 255) / 256;
+  if (strip_off || tn < 2) return 0;
+  int64_t best_m = 0;
+  double best = (double)(tm * tn);
+  for (int64_t m = tn - 1; m >= 1 && m >= tn - 3; --m) {
+    const int64_t rest = N - m * 256;
+    const int64_t strip_tiles = ((M + 127) / 128) * ((rest + 127) / 128);
+    const double cut = (double)(tm * m) + kRing128TileTime * (double)strip_tiles;
+    if (cut < best) best = cut, best_m = m;
+  }
+  return best_m * 256;
+}
+
 // ---- split-bf16 (gemm_bf16x3.hpp: launch_gemm3_nt) -------------------------------------------------------------------------
 enum class G3Kernel {
   Reg128,   // gemm3_nt_kernel: 128 x 128 tiles staged through registers
@@ -100,8 +137,11 @@ struct G3Choice {
   int64_t cut;      // > 0: columns [0, cut) run as G3Part::Main, columns [cut, N) as G3Part::Strip
 };
 
-// A (M rows), B (N rows): split matrices of Kp (a multiple of 32) columns; `forced` = option g3_tile, 0 = by grid size
-inline G3Choice choose_g3(int64_t M, int64_t N, int64_t Kp, int64_t cus, int forced, bool strip_off, G3Part part) {
+// A (M rows), B (N rows): split matrices of Kp (a multiple of 32) columns; `forced` = option g3_tile, 0 = by grid size;
+// `shared`: the launch shares the chip with another stream, so the two big-tile choices (160-row tiles, the strip cut) go by chip
+// time instead of makespan; the small-grid rules are the same either way
+inline G3Choice choose_g3(int64_t M, int64_t N, int64_t Kp, int64_t cus, int forced, bool strip_off, G3Part part,
+                          bool shared = false) {
   const int64_t ns = Kp / 32;             // k-tiles
   const bool fit = fits(M, N, 4 * Kp);    // a row of a split matrix is 2 Kp bf16 = 4 Kp bytes, one 128-byte line per k-tile
   if (forced) {
@@ -114,13 +154,14 @@ inline G3Choice choose_g3(int64_t M, int64_t N, int64_t Kp, int64_t cus, int for
     return {forced == 256 ? G3Kernel::Dma256 : G3Kernel::Reg128, 0};
   }
   const bool ring64 = fit && ring_prefer(M, N, ns, cus);  // small grids with long k loops
-  const bool w4 = fit && w4_prefer(M, N, cus);            // 150-tile GEMMs of the encoder: 240 items in one round
+  // 150-tile GEMMs of the encoder: 240 items in one round (on a shared chip: 240 items x 0.85 against 150 tiles, so not there)
+  const bool w4 = fit && (shared ? w4_prefer_shared(M, N, cus) : w4_prefer(M, N, cus));
   const bool big = fit && worth_it(M, N, cus);
   const bool ring128 = fit && ns >= 8;
   // a strip is priced as 128 x 128 tiles and runs as such unless the 64 x 64 ring wants it: no big-tile rule applies to it
   if (part == G3Part::Strip && ring128 && !ring64) return {G3Kernel::Ring128, 0};
   if (part == G3Part::Whole && big && !w4 && !ring64) {
-    const int64_t c0 = strip_split_columns(M, N, cus, strip_off);
+    const int64_t c0 = shared ? strip_split_columns_shared(M, N, strip_off) : strip_split_columns(M, N, cus, strip_off);
     if (c0 > 0) return {G3Kernel::Phase8, c0};
   }
   if (ring64) return {G3Kernel::Ring64, 0};

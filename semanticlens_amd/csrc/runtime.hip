@@ -25,7 +25,7 @@ int hip_fail(hipError_t e, const char* what) {
 }
 
 // ---- variant switches ---------------------------------------------------------------------------------------------------
-static const char* const kOptNames[OPT_COUNT] = {"g3_tile", "f32_tile", "g3_strip_off", "colreduce_nw", "bn_policy"};
+static const char* const kOptNames[OPT_COUNT] = {"g3_tile", "f32_tile", "g3_strip_off", "colreduce_nw", "bn_policy", "g3_shared"};
 static std::atomic<int64_t> g_opts[OPT_COUNT];
 static std::once_flag g_opts_once;
 
@@ -96,7 +96,7 @@ SL_API int sl_abi_version(void) { return SL_ABI_VERSION; }
 
 SL_API int sl_set_option(const char* name, int64_t value) {
   const int id = opt_id(name);
-  SL_REQUIRE(id >= 0, "sl_set_option: unknown option '%s' (g3_tile, f32_tile, g3_strip_off, colreduce_nw, bn_policy)", name ? name : "(null)");
+  SL_REQUIRE(id >= 0, "sl_set_option: unknown option '%s' (g3_tile, f32_tile, g3_strip_off, colreduce_nw, bn_policy, g3_shared)", name ? name : "(null)");
   (void)option(id);  // the environment is read first, once: an explicit call wins over it
   g_opts[id].store(value);
   return 0;
