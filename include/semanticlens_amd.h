@@ -465,7 +465,7 @@ int sl_condition_init(const float* d_act, int64_t B, int64_t C, int64_t S, int64
  * sl_activation_heat_boxes: P pairs (row d_rows[j], channel d_channels[j]) (int64, device) of a layer output d_act
  * (B,C,S) strided fp32 (sl_condition_init's convention; conv: S = H'*W', prefix 0, grid H' x W'; tokens: the (B,F,T)
  * view, the grid gh x gw starting at token `prefix`).  heat_j = max(bilinear upsample of act[u_j, c_j] to H x W
- * (F.interpolate, align_corners=False), 0); d_box (P,4) int32 = the box sl_render_heatmaps computes for that heat in
+ * (F.interpolate, align_corners=False; an axis of one cell is copied, not blended with itself), 0); d_box (P,4) int32 = the box sl_render_heatmaps computes for that heat in
  * SL_RENDER_CROP style (blur, |b| / max|b|, crop range, square box; the full image when nothing exceeds crop_th).
  * d_heat (P,H,W) the unblurred heat, written only when non-NULL.  sl_heat_boxes: the same box from a full-resolution
  * d_heat (P,H,W).  d_ws: sl_render_ws_bytes(P, H, W) bytes.  Refused before any launch as sl_render_heatmaps refuses

@@ -1659,7 +1659,10 @@ def render_heatmaps(rel: torch.Tensor, img: torch.Tensor, style: str, kernel_siz
     """K13 on ``rel`` (B, Cin, H, W) and ``img`` (B, 3, H, W) fp32 device tensors (same device) ->
     ``(heat (B, H, W) fp32 or None, box (B, 4) int32, flags (B,) int32, rgb (B, H, W, 3) uint8)``, all on the device.
     ``box`` is the square crop box (row1, row2, col1, col2), ``flags`` bit 0 = crop applied, bit 1 = mask non-empty; the
-    rendered image is ``rgb[b, :h, :w]`` with ``(h, w)`` the box clamped to the image when bit 0 is set, else (H, W)."""
+    rendered image is ``rgb[b, :h, :w]`` with ``(h, w)`` the box clamped to the image when bit 0 is set, else (H, W).
+    The limits on ``kernel_size`` and the plane are checked by the native call only: ``kernel_size`` even, below 1 or with
+    ``kernel_size // 2 >= min(H, W)`` raises ``ValueError``; ``kernel_size > 255`` or ``W + kernel_size - 1 > 16384`` raises
+    ``NativeLibraryError`` ("exceeds the supported maximum")."""
     if rel.ndim != 4 or img.ndim != 4 or img.shape[1] != 3 or rel.shape[0] != img.shape[0] or rel.shape[2:] != img.shape[2:]:
         raise ValueError(f"render_heatmaps: expected rel (B, Cin, H, W) and img (B, 3, H, W), got {tuple(rel.shape)} and {tuple(img.shape)}")
     if style not in RENDER_STYLES:

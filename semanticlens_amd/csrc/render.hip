@@ -372,8 +372,16 @@ struct UpsampledActHeat {
       const float w1l = wr - (float)w1, w0l = 1.f - w1l;
       const float* r0 = a + (int64_t)h1 * gw * ss;
       const float* r1 = a + (int64_t)(h1 + h1p) * gw * ss;
-      v = h0l * (w0l * r0[(int64_t)w1 * ss] + w1l * r0[(int64_t)(w1 + w1p) * ss]) +
-          h1l * (w0l * r1[(int64_t)w1 * ss] + w1l * r1[(int64_t)(w1 + w1p) * ss]);
+      // an axis of one cell has nothing to interpolate: ATen blends the cell with itself, l0 * a + l1 * a, a few ulp off a
+      if (gh == 1 && gw == 1)
+        v = r0[0];
+      else if (gh == 1)
+        v = w0l * r0[(int64_t)w1 * ss] + w1l * r0[(int64_t)(w1 + w1p) * ss];
+      else if (gw == 1)
+        v = h0l * r0[0] + h1l * r1[0];
+      else
+        v = h0l * (w0l * r0[(int64_t)w1 * ss] + w1l * r0[(int64_t)(w1 + w1p) * ss]) +
+            h1l * (w0l * r1[(int64_t)w1 * ss] + w1l * r1[(int64_t)(w1 + w1p) * ss]);
       v = fmaxf(v, 0.f);
     }
     if (out && own) out[(int64_t)y * W + x] = v;

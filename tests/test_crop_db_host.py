@@ -88,6 +88,14 @@ def test_activation_heat_boxes_rejects_bad_arguments_without_a_device():
     assert _boxes(k=0) == -1
     assert _boxes(H=2, k=5) == -1 and b"kernel_size // 2 = 2 must be smaller than H and W" in lib.sl_last_error()
     assert _boxes(k=257, H=300, W=300) == -3 and b"exceeds the supported maximum" in lib.sl_last_error()
+    # the limits themselves, for both entry points: W + kernel_size - 1 = 16384 fills the LDS tile; kernel_size 255 needs 128 x 128
+    assert _boxes(H=2, W=16382, k=3, P=0) == 0 and lib.sl_heat_boxes(FAKE, 0, 2, 16382, 3, 0.01, FAKE, FAKE, 0, None) == 0
+    assert _boxes(H=2, W=16383, k=3) == -3 and b"exceeds the supported maximum" in lib.sl_last_error()
+    assert lib.sl_heat_boxes(FAKE, 2, 2, 16383, 3, 0.01, FAKE, FAKE, 1 << 30, None) == -3
+    assert b"sl_heat_boxes: kernel_size 3 with W 16383 exceeds the supported maximum" in lib.sl_last_error()
+    assert _boxes(H=128, W=128, k=255, P=0) == 0 and lib.sl_heat_boxes(FAKE, 0, 128, 128, 255, 0.01, FAKE, FAKE, 0, None) == 0
+    assert _boxes(H=127, W=128, k=255) == -1 and b"kernel_size // 2 = 127 must be smaller than H and W" in lib.sl_last_error()
+    assert lib.sl_heat_boxes(FAKE, 2, 127, 128, 255, 0.01, FAKE, FAKE, 1 << 30, None) == -1
     for crop_th in (-0.1, 1.0, float("nan")):
         assert _boxes(crop_th=crop_th) == -1 and lib.sl_last_error() == b"'crop_th' must be between [0, 1)"
     assert _boxes(prefix=1) == -1 and b"does not fit S = 16" in lib.sl_last_error()

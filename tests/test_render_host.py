@@ -53,6 +53,11 @@ def test_render_rejects_bad_arguments_without_a_device():
     assert _render(style=3) == -1 and b"unknown style 3" in lib.sl_last_error()
     assert _render(ws_bytes=16) == -1 and b"workspace too small" in lib.sl_last_error()
     assert _render(k=257, H=300, W=300) == -3 and b"exceeds the supported maximum" in lib.sl_last_error()
+    # the limits themselves: W + kernel_size - 1 = 16384 fills the LDS tile; kernel_size 255 needs a 128 x 128 plane
+    assert _render(H=2, W=16382, k=3, B=0) == 0
+    assert _render(H=2, W=16383, k=3) == -3 and b"exceeds the supported maximum" in lib.sl_last_error()
+    assert _render(H=128, W=128, k=255, B=0) == 0
+    assert _render(H=127, W=128, k=255) == -1 and b"kernel_size // 2 = 127 must be smaller than H and W (127 x 128)" in lib.sl_last_error()
 
 
 def test_condition_init_rejects_bad_arguments_without_a_device():
