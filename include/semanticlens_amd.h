@@ -405,7 +405,8 @@ int sl_embed_tokens(const float* d_table, int64_t vocab, const int64_t* d_ids, i
  * writes h_plan (B, SL_PP_PLAN_STRIDE) int64 (upload it unchanged) and h_info[SL_PP_INFO_*].
  * sl_preprocess: d_pixels packed (h,w,3) uint8 images, d_plan the uploaded plan, max_h / coef_bytes from h_info,
  * h_mean/h_std 3 floats each (host); d_out (B,3,S,S) fp32 and/or d_out_u8 (B,S,S,3) resized+cropped bytes
- * (either may be NULL); d_ws of h_info[SL_PP_INFO_WS_BYTES] bytes. */
+ * (either may be NULL); d_ws of h_info[SL_PP_INFO_WS_BYTES] bytes.  Every refusal (a max_h too tall for the grid
+ * included) returns before the first kernel is launched. */
 #define SL_PP_SHORTEST 0
 #define SL_PP_SQUASH 1
 #define SL_PP_BICUBIC 0

@@ -421,6 +421,8 @@ SL_API int sl_preprocess(const uint8_t* d_pixels, const int64_t* d_plan, int64_t
   SL_REQUIRE(!d_out || (h_mean && h_std), "sl_preprocess: mean/std required for the float output");
   SL_REQUIRE(coef_bytes >= 0 && (size_t)coef_bytes <= ws_bytes && (coef_bytes & 15) == 0, "sl_preprocess: bad workspace split");
   SL_REQUIRE(B <= 65535, "sl_preprocess: at most 65535 images per call");
+  const int64_t hb = ((max_h + kRowsPerThread - 1) / kRowsPerThread * S + 255) / 256;
+  SL_REQUIRE(hb < (1ll << 23), "sl_preprocess: image too tall");
   hipStream_t st = (hipStream_t)stream;
   int32_t* coef = static_cast<int32_t*>(d_ws);
   uint8_t* tmp = static_cast<uint8_t*>(d_ws) + coef_bytes;
@@ -431,8 +433,6 @@ SL_API int sl_preprocess(const uint8_t* d_pixels, const int64_t* d_plan, int64_t
   }
   hipLaunchKernelGGL(coeff_kernel, dim3(2, (unsigned)B), dim3(256), 0, st, d_plan, S, interp, coef);
   SL_CHECK_HIP(hipGetLastError());
-  const int64_t hb = ((max_h + kRowsPerThread - 1) / kRowsPerThread * S + 255) / 256;
-  SL_REQUIRE(hb < (1ll << 23), "sl_preprocess: image too tall");
   if (hb > 0) {
     hipLaunchKernelGGL(horizontal_kernel, dim3((unsigned)hb, (unsigned)B), dim3(256), 0, st, d_pixels, d_plan, S, coef, tmp);
     SL_CHECK_HIP(hipGetLastError());
