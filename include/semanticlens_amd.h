@@ -544,6 +544,32 @@ int sl_mutualmax_finish(const uint64_t* d_state, int64_t n, float* d_vals, int64
 int sl_segmax_merge(uint64_t* d_state, int64_t state_ld, int64_t G, int64_t R, int64_t B, const float* d_cand, int64_t ld,
                     const int32_t* d_row_seg, int64_t row_id_base, void* stream);
 
+/* ---- K24: redundancy groups — which components the redundancy score (reference scores.py:51-81) counts as
+ * duplicates of each other.  No reference counterpart.  A group is a connected component of the graph "cosine >= threshold" over the
+ * n components of one layer.  State: d_parent (n,) int32, a union-find forest in which a root always hangs under a SMALLER root
+ * (parent[x] <= x at every instant; csrc/unionfind.hpp), d_degree (n,) int32, and one int32 status word, raised if a loop ever passed
+ * its cap of n + 1 steps; read it once, after the last tile.  n <= 2^31 - 1.
+ *
+ * sl_unionfind_init writes the empty state: parent[i] = i, degree = 0, status = 0. */
+int sl_unionfind_init(int32_t* d_parent, int32_t* d_degree, int32_t* d_status, int64_t n, void* stream);
+/* Fold a tile as sl_mutualmax_merge reads one (R rows of B fp32 columns, row stride ld >= B, any 4-byte aligned start): row r has the
+ * id row_id_base + r, column c the id col_id_base + c, all within [0, n).  An element is an edge iff row id < column id and
+ * v >= threshold (finite): a NaN is never an edge, a tie at the threshold is, the diagonal and what lies left of it are ignored, so a
+ * walk over the upper triangle counts every pair once.  Every edge joins the two groups and adds one to both degrees.  A tile with
+ * no element right of the diagonal, R == 0 or B == 0 is a no-op without a launch. */
+int sl_threshold_union_merge(int32_t* d_parent, int32_t* d_degree, int32_t* d_status, int64_t n, const float* d_cand, int64_t ld,
+                             int64_t R, int64_t B, int64_t row_id_base, int64_t col_id_base, float threshold, void* stream);
+/* parent[i] = the root above i, idempotent.  Between tiles it keeps the chains short; after the last tile d_parent IS the labels: every
+ * component carries the smallest id of its group.  What d_parent holds before that depends on scheduling; the labels and the
+ * degrees do not. */
+int sl_unionfind_flatten(int32_t* d_parent, int64_t n, int32_t* d_status, void* stream);
+/* The optional second pass over the same tiles, with the final labels: d_state (n,) uint32, 0xFFFFFFFF = empty, receives at
+ * state[label] the minimum order key (K17's) over the upper-triangle elements whose row and column carry that label. */
+int sl_group_min_merge(uint32_t* d_state, const int32_t* d_labels, int64_t n, const float* d_cand, int64_t ld, int64_t R, int64_t B,
+                       int64_t row_id_base, int64_t col_id_base, void* stream);
+/* d_cohesion[i] = the value of state[labels[i]]: the smallest pairwise cosine inside i's group, NaN for an empty entry (a singleton). */
+int sl_group_min_finish(const uint32_t* d_state, const int32_t* d_labels, int64_t n, float* d_cohesion, void* stream);
+
 /* normalize(x) @ normalize(y)^T for ANY shapes — x (M,K), y (N,K), out (M,N) — with K6's kernels and arithmetic mode
  * (sl_set_gemm_mode) and none of similarity_score's shape branches: what the tiled top-k probing calls per tile.
  * d_ws: sl_cosine_nt_ws_bytes(M,N,K) bytes. */
@@ -560,7 +586,7 @@ size_t sl_cosine_nt_ws_bytes(int64_t M, int64_t N, int64_t K);
 #define SL_PROF_GATHER 3
 #define SL_PROF_SCORES 4
 #define SL_PROF_BATCHNORM 5 /* K16 fused inference BatchNorm; launches = BatchNorm2d evaluations (K19) */
-#define SL_PROF_TOPK 6 /* K17 streaming fp32 top-k; K20 mutual best matches; K22 per-segment maxima */
+#define SL_PROF_TOPK 6 /* K17 streaming fp32 top-k; K20 mutual best matches; K22 per-segment maxima; K24 redundancy groups */
 #define SL_PROF_NFAM 7
 int sl_prof_enable(int on);
 int sl_prof_reset(void);

@@ -11,8 +11,8 @@ from __future__ import annotations
 from semanticlens_amd import foundation_models, scores, utils
 from semanticlens_amd.lens import (ConceptAudit, ConceptDBComparison, Lens, audit_concepts, compare_concept_dbs, label_facets,
                                    probe_setmax, search_facets)
-from semanticlens_amd.scores import (Facets, clarity_score, polysemanticity_facets, polysemanticity_score, redundancy_score,
-                                     silhouette_samples, silhouette_score)
+from semanticlens_amd.scores import (Facets, RedundancyGroups, clarity_score, polysemanticity_facets, polysemanticity_score,
+                                     redundancy_groups, redundancy_score, silhouette_samples, silhouette_score)
 
 __version__ = "0.1.0"
 
@@ -29,6 +29,8 @@ __all__ = [
     "clarity_score",
     "polysemanticity_score",
     "redundancy_score",
+    "redundancy_groups",
+    "RedundancyGroups",
     "Facets",
     "polysemanticity_facets",
     "label_facets",

@@ -8,6 +8,7 @@ device, the call raises.  PyTorch is used for device memory and streams only
 from __future__ import annotations
 
 import ctypes
+import math
 import operator
 import os
 from pathlib import Path
@@ -131,6 +132,11 @@ SIGNATURES = {
     "sl_mutualmax_merge": (_int, [_vp, _vp, _i64, _i64, _vp, _i64, _i64, _i64, _vp]),
     "sl_mutualmax_finish": (_int, [_vp, _i64, _vp, _vp, _vp]),
     "sl_segmax_merge": (_int, [_vp, _i64, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _vp]),
+    "sl_unionfind_init": (_int, [_vp, _vp, _vp, _i64, _vp]),
+    "sl_threshold_union_merge": (_int, [_vp, _vp, _vp, _i64, _vp, _i64, _i64, _i64, _i64, _i64, ctypes.c_float, _vp]),
+    "sl_unionfind_flatten": (_int, [_vp, _i64, _vp, _vp]),
+    "sl_group_min_merge": (_int, [_vp, _vp, _i64, _vp, _i64, _i64, _i64, _i64, _i64, _vp]),
+    "sl_group_min_finish": (_int, [_vp, _vp, _i64, _vp, _vp]),
     "sl_cosine_nt": (_int, [_vp, _i64, _vp, _i64, _i64, _vp, _vp, _sz, _vp]),
     "sl_cosine_nt_ws_bytes": (_sz, [_i64, _i64, _i64]),
     "sl_prof_enable": (_int, [_int]),
@@ -933,15 +939,17 @@ def tile_walk(m: int, n: int, rows: int, cols: int):
             yield r0, min(rows, m - r0), c0, min(cols, n - c0)
 
 
-def _cosine_tiles(xd: torch.Tensor, yd: torch.Tensor, rows: int, cols: int):
+def _cosine_tiles(xd: torch.Tensor, yd: torch.Tensor, rows: int, cols: int, walk=None):
     """``normalize(xd) @ normalize(yd).T`` one ``tile_walk`` rectangle at a time, as ``(r0, nr, c0, nc, out)``: the cosine GEMM (K6)
     writes ``out (nr, nc)`` into ONE reused buffer, with one reused workspace (both allocated by the call, before anything is
-    iterated), on the operands' stream; the consumer folds it on that stream before asking for the next."""
+    iterated), on the operands' stream; the consumer folds it on that stream before asking for the next.  ``walk``: another
+    walk of rectangles of at most ``(rows, cols)`` (``upper_tile_walk``)."""
+    walk = walk if walk is not None else tile_walk(xd.shape[0], yd.shape[0], rows, cols)
     tile = torch.empty(rows * cols, dtype=torch.float32, device=xd.device)
     ws = torch.empty(int(lib().sl_cosine_nt_ws_bytes(rows, cols, xd.shape[1])), dtype=torch.uint8, device=xd.device)
 
     def tiles():
-        for r0, nr, c0, nc in tile_walk(xd.shape[0], yd.shape[0], rows, cols):
+        for r0, nr, c0, nc in walk:
             out = tile[: nr * nc].view(nr, nc)
             cosine_nt(xd[r0 : r0 + nr], yd[c0 : c0 + nc], out, ws)
             yield r0, nr, c0, nc, out
@@ -1119,6 +1127,151 @@ def setmax_finish(state: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
         raise ValueError(f"setmax_finish: a state is a (G, C) int64 device tensor, got {tuple(state.shape)}")
     vals, ids = mutualmax_finish(state.contiguous().view(-1))
     return vals.view(state.shape), ids.view(state.shape)
+
+
+# ------------------------------------------------------------------------------------------------
+# K24: redundancy groups (the connected components of "cosine >= threshold" and every component's degree)
+# ------------------------------------------------------------------------------------------------
+REDGROUPS_MAX_N = (1 << 31) - 1  # the forest's entries are int32 ids
+
+
+def upper_tile_walk(n: int, rows: int, cols: int):
+    """The ``(r0, nr, c0, nc)`` rectangles that cover the upper triangle of an ``(n, n)`` matrix: for the row block at ``r0``
+    they start at column ``r0 - r0 % 4`` and run to ``n`` in steps of ``cols``, rounded up to a multiple of 4 so that every
+    rectangle starts on one.  Every pair ``i < j`` lies in exactly one rectangle; a rectangle that would hold none is left out;
+    nothing left of the diagonal block is multiplied."""
+    cols = -(-cols // 4) * 4
+    for r0 in range(0, n, rows):
+        for c0 in range(r0 - r0 % 4, n, cols):
+            nc = min(cols, n - c0)
+            if c0 + nc - 1 > r0:
+                yield r0, min(rows, n - r0), c0, nc
+
+
+def check_threshold(threshold) -> float:
+    """A finite float, before a device is touched."""
+    try:
+        threshold = float(threshold)
+    except (TypeError, ValueError):
+        raise ValueError(f"threshold must be a finite float, got {threshold!r}") from None
+    if not math.isfinite(threshold):
+        raise ValueError(f"threshold must be a finite float, got {threshold!r}")
+    return threshold
+
+
+def _check_states(what: str, *states) -> int:
+    """K24's states: 1-D int32 device tensors with unit stride, all on one device and of one length, which is returned."""
+    first = states[0]
+    for s in states:
+        if (s.ndim != 1 or s.dtype != torch.int32 or not s.is_cuda or s.device != first.device or s.shape != first.shape
+                or (s.numel() > 1 and s.stride(0) != 1)):
+            raise ValueError(f"{what}: a state is a 1-D int32 device tensor with unit stride, all on one device and of one length, "
+                             f"got {tuple(s.shape)} {s.dtype} on {s.device}")
+    return first.shape[0]
+
+
+def _check_status(what: str, status: torch.Tensor, device):
+    if tuple(status.shape) != (1,) or status.dtype != torch.int32 or status.device != device:
+        raise ValueError(f"{what}: the status word is one int32 on {device}, got {tuple(status.shape)} {status.dtype} on {status.device}")
+
+
+def _check_tile(what: str, cand: torch.Tensor, device):
+    if cand.ndim != 2 or cand.dtype != torch.float32 or cand.device != device:
+        raise ValueError(f"{what}: the candidate tile must be a 2-D float32 tensor on {device}, got {tuple(cand.shape)} {cand.dtype} "
+                         f"on {cand.device}")
+
+
+def unionfind_new(n: int, device) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """The empty state ``(parent (n,), degree (n,), status (1,))``, all int32: ``parent[i] = i``, zeros."""
+    parent = torch.empty(n, dtype=torch.int32, device=device)
+    degree = torch.empty(n, dtype=torch.int32, device=device)
+    status = torch.empty(1, dtype=torch.int32, device=device)
+    with _on(parent.device):
+        _check(lib().sl_unionfind_init(_ptr(parent), _ptr(degree), _ptr(status), n, _stream(parent)), "sl_unionfind_init")
+    return parent, degree, status
+
+
+def threshold_union_merge(parent: torch.Tensor, degree: torch.Tensor, status: torch.Tensor, cand: torch.Tensor, threshold: float,
+                          row_id_base: int = 0, col_id_base: int = 0):
+    """Fold the ``(R, B)`` fp32 tile ``cand`` (unit column stride, any row stride) into the forest and the degrees of ``n``
+    components: every element with ``row_id_base + r < col_id_base + c`` and a value ``>= threshold`` is an edge."""
+    n = _check_states("threshold_union_merge", parent, degree)
+    _check_status("threshold_union_merge", status, parent.device)
+    _check_tile("threshold_union_merge", cand, parent.device)
+    R, B = cand.shape
+    cand, ld = _tile_view(cand)
+    with _on(cand.device):
+        rc = lib().sl_threshold_union_merge(_ptr(parent), _ptr(degree), _ptr(status), n, _ptr(cand), ld, R, B, row_id_base, col_id_base,
+                                            check_threshold(threshold), _stream(cand))
+    _check(rc, "sl_threshold_union_merge")
+
+
+def unionfind_flatten(parent: torch.Tensor, status: torch.Tensor):
+    """``parent[i] = `` its root.  After the last tile ``parent`` holds the labels: the smallest id of every component's group."""
+    _check_states("unionfind_flatten", parent)
+    _check_status("unionfind_flatten", status, parent.device)
+    with _on(parent.device):
+        _check(lib().sl_unionfind_flatten(_ptr(parent), parent.shape[0], _ptr(status), _stream(parent)), "sl_unionfind_flatten")
+
+
+def group_min_merge(state: torch.Tensor, labels: torch.Tensor, cand: torch.Tensor, row_id_base: int = 0, col_id_base: int = 0):
+    """Fold the tile into ``state (n,)`` int32 (``torch.full(-1)`` is the empty state): entry ``label`` takes the smallest order
+    key among the upper-triangle elements whose row and column both carry ``label`` in ``labels (n,)`` int32."""
+    n = _check_states("group_min_merge", state, labels)
+    _check_tile("group_min_merge", cand, state.device)
+    R, B = cand.shape
+    cand, ld = _tile_view(cand)
+    with _on(cand.device):
+        rc = lib().sl_group_min_merge(_ptr(state), _ptr(labels), n, _ptr(cand), ld, R, B, row_id_base, col_id_base, _stream(cand))
+    _check(rc, "sl_group_min_merge")
+
+
+def group_min_finish(state: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
+    """``(n,)`` float32: the value at ``state[labels[i]]``, NaN for the empty entry."""
+    n = _check_states("group_min_finish", state, labels)
+    out = torch.empty(n, dtype=torch.float32, device=labels.device)
+    with _on(labels.device):
+        _check(lib().sl_group_min_finish(_ptr(state), _ptr(labels), n, _ptr(out), _stream(labels)), "sl_group_min_finish")
+    return out
+
+
+def redundancy_probe(x: torch.Tensor, threshold: float, chunk_rows: int | None = None, chunk_cols: int | None = None,
+                     cohesion: bool = False):
+    """The connected components of the graph "cosine >= threshold" over the rows of ``x (C, D)``, as ``(labels (C,) int64,
+    degree (C,) int32, cohesion (C,) float32 | None)``: a row's label is the smallest row id of its group, its degree the number
+    of OTHER rows at or above the threshold, its cohesion the smallest pairwise cosine inside its group (NaN for a singleton).
+    A NaN cosine is never an edge, a tie at the threshold is, the diagonal is not.
+
+    The cosine GEMM (K6, in the arithmetic ``set_gemm_mode`` selects) writes one reused tile of the ``upper_tile_walk`` — the
+    upper triangle only, about half the products of ``mutual_probe(x, x)`` — and K24 folds it into a union-find forest and the
+    degrees on the same stream, then flattens the forest, so that the chains are short for the next tile and the flatten after
+    the last tile leaves the labels.  The status word is read once, at the end.  ``cohesion=True`` walks the tiles a second
+    time with the final labels.  ``tile_plan`` has the default tile."""
+    threshold = check_threshold(threshold)
+    _check_probe_args("redundancy_probe", x, x, chunk_rows=chunk_rows, chunk_cols=chunk_cols)
+    n = x.shape[0]
+    if n > REDGROUPS_MAX_N:
+        raise ValueError(f"redundancy_probe: more than {REDGROUPS_MAX_N} rows do not fit the forest's int32 ids")
+    xd = _f32c(x)
+    if n < 2:  # nothing to pair: no launch
+        labels = torch.zeros(n, dtype=torch.int64, device=xd.device)
+        nan = torch.full((n,), float("nan"), dtype=torch.float32, device=xd.device) if cohesion else None
+        return labels, torch.zeros(n, dtype=torch.int32, device=xd.device), nan
+    rows, cols = tile_plan(n, n, chunk_rows, chunk_cols)
+    cols = -(-cols // 4) * 4  # the walk's step
+    parent, degree, status = unionfind_new(n, xd.device)
+    for r0, _, c0, _, out in _cosine_tiles(xd, xd, rows, cols, upper_tile_walk(n, rows, cols)):
+        threshold_union_merge(parent, degree, status, out, threshold, r0, c0)
+        unionfind_flatten(parent, status)
+    if int(status.item()):
+        raise RuntimeError("redundancy_probe: a union-find loop passed its cap of n + 1 steps; the forest's invariant was broken")
+    coh = None
+    if cohesion:
+        state = torch.full((n,), -1, dtype=torch.int32, device=xd.device)
+        for r0, _, c0, _, out in _cosine_tiles(xd, xd, rows, cols, upper_tile_walk(n, rows, cols)):
+            group_min_merge(state, parent, out, r0, c0)
+        coh = group_min_finish(state, parent)
+    return parent.to(torch.int64), degree, coh
 
 
 # ------------------------------------------------------------------------------------------------

@@ -136,6 +136,76 @@ class Facets:
         return (torch.div(rows, kc, rounding_mode="floor").masked_fill(empty, -1), (rows % kc).masked_fill(empty, -1))
 
 
+@dataclass
+class RedundancyGroups:
+    """What ``redundancy_groups`` returns: which components of a layer duplicate each other.  A group is a connected component of
+    the graph "cosine >= threshold" over the layer's aggregated concept DB — the quantity ``redundancy_score`` averages, kept
+    per pair.  Every tensor lives on the DB's device.
+
+    * ``labels (C,)`` int64: the SMALLEST component id of the component's group; a singleton labels itself.
+    * ``degree (C,)`` int32: how many OTHER components have a cosine at or above the threshold to this one.
+    * ``cohesion (C,)`` float32 or ``None``: the smallest pairwise cosine inside the component's group, NaN for a singleton.
+      Connected components chain — two members of one group may be far below the threshold to each other — and this is where
+      it shows; it costs a second pass over the cosine tiles, so it is computed only on request."""
+
+    labels: torch.Tensor
+    degree: torch.Tensor
+    cohesion: torch.Tensor | None = None
+
+    @property
+    def redundant(self) -> torch.Tensor:
+        """``(C,)`` bool: the component has at least one near-duplicate."""
+        return self.degree > 0
+
+    @property
+    def sizes(self) -> torch.Tensor:
+        """``(C,)`` int64: the size of each component's group."""
+        return torch.bincount(self.labels, minlength=self.labels.shape[0])[self.labels]
+
+    @property
+    def n_groups(self) -> int:
+        """How many distinct concepts the layer holds at this threshold."""
+        return int((self.labels == torch.arange(self.labels.shape[0], device=self.labels.device)).sum())
+
+    def members(self, i: int) -> torch.Tensor:
+        """The ids of the group of component ``i``, ascending."""
+        return torch.nonzero(self.labels == self.labels[i]).flatten()
+
+    def representatives(self, by: str = "degree") -> torch.Tensor:
+        """One id per group, ascending by label.  ``by="degree"``: the member of largest degree (ties: the smaller id), the
+        component closest to the most others; ``by="label"``: the label itself."""
+        if by not in ("degree", "label"):
+            raise ValueError(f"by={by!r}: \"degree\" or \"label\"")
+        C = self.labels.shape[0]
+        ids = torch.arange(C, device=self.labels.device)
+        roots = ids[self.labels == ids]
+        if by == "label":
+            return roots
+        key = self.degree.to(torch.int64) * C + (C - 1 - ids)  # larger degree first, then the smaller id
+        best = torch.zeros(C, dtype=torch.int64, device=self.labels.device).scatter_reduce(0, self.labels, key, "amax")
+        return C - 1 - best[roots] % C
+
+    def prune(self, db: torch.Tensor) -> torch.Tensor:
+        """``db[representatives()]``: one row per group."""
+        return db[self.representatives().to(db.device)]
+
+
+@torch.inference_mode()
+def redundancy_groups(cones, threshold=0.9, cohesion=False, chunk_rows=None, chunk_cols=None) -> RedundancyGroups:
+    """Which components ``redundancy_score`` (reference scores.py:51-81) counts as duplicates of each other: the groups of the
+    ``(C, D)`` aggregated concept DB ``cones`` under "cosine >= threshold" (``RedundancyGroups``).  A NaN cosine is never an
+    edge (a component with a NaN or infinite coordinate is a singleton of degree 0), a zero row has cosine 0 to everything, a
+    tie at exactly ``threshold`` is an edge, the diagonal is not.  Deterministic: no ``k``, no random start.
+
+    Kernel K24 folds each tile of the cosine GEMM's upper triangle into a union-find forest and the degrees
+    (``_native.redundancy_probe``); the ``(C, C)`` matrix never exists.  ``cohesion=True`` adds a second pass."""
+    threshold = N.check_threshold(threshold)
+    if cones.ndim != 2:
+        raise ValueError("redundancy_groups expects a (n_components, n_features) tensor")
+    labels, degree, coh = N.redundancy_probe(cones, threshold, chunk_rows, chunk_cols, cohesion)
+    return RedundancyGroups(labels.to(cones.device), degree.to(cones.device), None if coh is None else coh.to(cones.device))
+
+
 @torch.inference_mode()
 def silhouette_samples(V, labels, metric="euclidean"):
     """scikit-learn's ``silhouette_samples`` for every component: ``V (C, n, D)``, ``labels (C, n)`` or ``(m, C, n)`` int32 ->
