@@ -570,6 +570,32 @@ int sl_group_min_merge(uint32_t* d_state, const int32_t* d_labels, int64_t n, co
 /* d_cohesion[i] = the value of state[labels[i]]: the smallest pairwise cosine inside i's group, NaN for an empty entry (a singleton). */
 int sl_group_min_finish(const uint32_t* d_state, const int32_t* d_labels, int64_t n, float* d_cohesion, void* stream);
 
+/* ---- K25: streaming softmax statistics over cosine tiles — the reduction behind label_distribution ------
+ * No reference counterpart.  For a row with the candidates c_j and the logits l_j = scale * c_j the state is FOUR doubles,
+ * d_state[4 r .. 4 r + 3] = (m, a, b, n): m = max l_j, a = sum exp(l_j - m), b = sum (l_j - m) exp(l_j - m), n = the number of
+ * candidates folded (-inf and NaN included).  log_z = m + log a, entropy = log a - b / a (nats), p_j = exp(l_j - log_z).
+ * Special values follow torch.logsumexp / torch.softmax in float64 and are told apart by m: a -inf candidate adds to n only; a
+ * row that saw a NaN has m = a = b = NaN; one that saw +inf (and no NaN) m = +inf, a = b = NaN; one that saw nothing above -inf
+ * m = -inf, a = b = 0.  The rule that merges two states is csrc/softmax_state.hpp's (host-checkable); NaN and +inf are absorbing
+ * whatever the order.  No floating-point atomics: the same sequence of calls gives the same bits.  The states after two cuts of
+ * the same candidates into tiles agree within the bound of DESIGN.md §K25, not bit for bit.
+ *
+ * sl_softmax_init writes the empty state (-inf, 0, 0, 0).  d_state is 8-byte aligned; R == 0 is a no-op everywhere. */
+int sl_softmax_init(double* d_state, int64_t R, void* stream);
+/* Fold a tile read exactly as sl_topk_merge reads one: R rows of B >= 1 fp32 columns, row stride ld >= B elements, any 4-byte
+ * aligned start, nothing outside [0, B) of a row touched.  scale must be finite and > 0 (and scale * log2 e a normal fp32 number).
+ * d_ws: sl_softmax_merge_ws_bytes(R,B) bytes (0 for most shapes: few rows of many columns are split over several wavefronts per
+ * row, whose partial states live there and are folded in a fixed order). */
+int sl_softmax_merge(double* d_state, int64_t R, const float* d_cand, int64_t ld, int64_t B, double scale, void* d_ws,
+                     size_t ws_bytes, void* stream);
+size_t sl_softmax_merge_ws_bytes(int64_t R, int64_t B);
+/* d_log_z (R,) and d_entropy (R,) float64: (-inf, NaN) for a row that saw nothing above -inf, (+inf, NaN) after a +inf, (NaN, NaN)
+ * after a NaN.  d_vals (R,k): K17's sorted values of the same candidates, or NULL when only the statistics are wanted;
+ * d_probs[r,i] = exp(scale * d_vals[r,i] - log_z[r]) as fp32, NaN where log_z[r] is not finite, and 0 for an empty slot (i >= n:
+ * the state's count tells an empty slot from a real -inf candidate). */
+int sl_softmax_finish(const double* d_state, int64_t R, double scale, const float* d_vals, int64_t k, float* d_probs,
+                      double* d_log_z, double* d_entropy, void* stream);
+
 /* normalize(x) @ normalize(y)^T for ANY shapes — x (M,K), y (N,K), out (M,N) — with K6's kernels and arithmetic mode
  * (sl_set_gemm_mode) and none of similarity_score's shape branches: what the tiled top-k probing calls per tile.
  * d_ws: sl_cosine_nt_ws_bytes(M,N,K) bytes. */
@@ -587,7 +613,8 @@ size_t sl_cosine_nt_ws_bytes(int64_t M, int64_t N, int64_t K);
 #define SL_PROF_SCORES 4
 #define SL_PROF_BATCHNORM 5 /* K16 fused inference BatchNorm; launches = BatchNorm2d evaluations (K19) */
 #define SL_PROF_TOPK 6 /* K17 streaming fp32 top-k; K20 mutual best matches; K22 per-segment maxima; K24 redundancy groups */
-#define SL_PROF_NFAM 7
+#define SL_PROF_SOFTMAX 7 /* K25 streaming softmax statistics */
+#define SL_PROF_NFAM 8
 int sl_prof_enable(int on);
 int sl_prof_reset(void);
 /* total_ms: sum of event-bracketed durations; launches: count; bytes: algorithmic bytes

@@ -9,8 +9,8 @@ HIP device, compute calls raise.
 from __future__ import annotations
 
 from semanticlens_amd import foundation_models, scores, utils
-from semanticlens_amd.lens import (ConceptAudit, ConceptDBComparison, Lens, audit_concepts, compare_concept_dbs, label_facets,
-                                   probe_setmax, search_facets)
+from semanticlens_amd.lens import (ConceptAudit, ConceptDBComparison, LabelDistribution, Lens, audit_concepts, compare_concept_dbs,
+                                   label_distribution, label_facets, probe_setmax, probe_softmax, search_facets)
 from semanticlens_amd.scores import (Facets, RedundancyGroups, clarity_score, polysemanticity_facets, polysemanticity_score,
                                      redundancy_groups, redundancy_score, silhouette_samples, silhouette_score)
 
@@ -26,6 +26,9 @@ __all__ = [
     "audit_concepts",
     "ConceptAudit",
     "probe_setmax",
+    "label_distribution",
+    "LabelDistribution",
+    "probe_softmax",
     "clarity_score",
     "polysemanticity_score",
     "redundancy_score",

@@ -25,6 +25,7 @@ SL_TOK_MEAN, SL_TOK_ABSMEAN, SL_TOK_MAX, SL_TOK_ABSMAX, SL_TOK_TOKEN = 0, 1, 2, 
 SL_TIES_TOTAL, SL_TIES_ATEN = 0, 1
 SL_MAX_SLOTS = 16
 SL_PROF_REDUCE, SL_PROF_MERGE, SL_PROF_GEMM, SL_PROF_GATHER, SL_PROF_SCORES, SL_PROF_BATCHNORM, SL_PROF_TOPK = 0, 1, 2, 3, 4, 5, 6
+SL_PROF_SOFTMAX = 7
 SL_ACT_NONE, SL_ACT_GELU, SL_ACT_QUICKGELU, SL_ACT_GELU_TANH = 0, 1, 2, 3
 TIE_MODES = {"total": SL_TIES_TOTAL, "aten": SL_TIES_ATEN}
 SL_PP_PLAN_STRIDE = 16
@@ -129,6 +130,10 @@ SIGNATURES = {
     "sl_topk_merge": (_int, [_vp, _vp, _i64, _i64, _vp, _i64, _i64, _i64, _vp, _sz, _vp]),
     "sl_topk_merge_ws_bytes": (_sz, [_i64, _i64, _i64]),
     "sl_topk_merge_states": (_int, [_vp, _vp, _i64, _i64, _vp, _vp, _i64, _vp]),
+    "sl_softmax_init": (_int, [_vp, _i64, _vp]),
+    "sl_softmax_merge": (_int, [_vp, _i64, _vp, _i64, _i64, ctypes.c_double, _vp, _sz, _vp]),
+    "sl_softmax_merge_ws_bytes": (_sz, [_i64, _i64]),
+    "sl_softmax_finish": (_int, [_vp, _i64, ctypes.c_double, _vp, _i64, _vp, _vp, _vp, _vp]),
     "sl_mutualmax_merge": (_int, [_vp, _vp, _i64, _i64, _vp, _i64, _i64, _i64, _vp]),
     "sl_mutualmax_finish": (_int, [_vp, _i64, _vp, _vp, _vp]),
     "sl_segmax_merge": (_int, [_vp, _i64, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _vp]),
@@ -980,6 +985,110 @@ def topk_probe(x: torch.Tensor, y: torch.Tensor, k: int, chunk_rows: int | None 
     for _, _, c0, _, out in tiles:
         topk_merge(vals, ids, out, id_base + c0, merge_ws)
     return vals, ids
+
+
+# ------------------------------------------------------------------------------------------------
+# K25: streaming softmax statistics over the same cosine tiles
+# ------------------------------------------------------------------------------------------------
+SOFTMAX_STATE_WIDTH = 4  # doubles per row: (m, a, b, n) (include/semanticlens_amd.h, csrc/softmax_state.hpp)
+_LOG2E = 1.4426950408889634
+_F32_MIN_NORMAL, _F32_MAX = 1.1754943508222875e-38, 3.4028234663852886e38
+
+
+def check_logit_scale(scale) -> float:
+    """``scale`` as a float: a finite number above 0 (``scale * log2 e`` a normal fp32 number), else ``ValueError``."""
+    try:
+        if isinstance(scale, (str, bytes)):
+            raise TypeError
+        value = float(scale)
+    except (TypeError, ValueError):
+        raise ValueError(f"logit_scale must be a number, got {scale!r}") from None
+    if not math.isfinite(value) or value <= 0:
+        raise ValueError(f"logit_scale = {value} must be finite and > 0")
+    if not _F32_MIN_NORMAL <= value * _LOG2E <= _F32_MAX:
+        raise ValueError(f"logit_scale = {value} leaves the range the kernel's fp32 exponent covers")
+    return value
+
+
+def _check_softmax_state(what: str, state: torch.Tensor, R: int | None = None):
+    if (state.ndim != 2 or state.shape[1] != SOFTMAX_STATE_WIDTH or state.dtype != torch.float64 or not state.is_cuda
+            or not state.is_contiguous()):
+        raise ValueError(f"{what}: a state is a contiguous (R, {SOFTMAX_STATE_WIDTH}) float64 device tensor, got {tuple(state.shape)} "
+                         f"{state.dtype} on {state.device}")
+    if R is not None and state.shape[0] != R:
+        raise ValueError(f"{what}: a state of {state.shape[0]} rows does not fit {R}")
+
+
+def softmax_new(R: int, device) -> torch.Tensor:
+    """Empty ``(R, 4)`` float64 state: ``(m, a, b, n) = (-inf, 0, 0, 0)`` per row."""
+    state = torch.empty((R, SOFTMAX_STATE_WIDTH), dtype=torch.float64, device=device)
+    with _on(state.device):
+        _check(lib().sl_softmax_init(_ptr(state), R, _stream(state)), "sl_softmax_init")
+    return state
+
+
+def softmax_merge(state: torch.Tensor, cand: torch.Tensor, scale: float, ws: torch.Tensor | None = None):
+    """Fold the ``(R, B)`` fp32 tile ``cand`` (unit column stride, any row stride), as logits ``scale * cand``, into the state.
+    ``ws``: a uint8 device buffer to use as the workspace of a split row when it is large enough."""
+    scale = check_logit_scale(scale)
+    if cand.ndim != 2 or cand.dtype != torch.float32 or not cand.is_cuda:
+        raise ValueError(f"softmax_merge: the candidate tile must be a 2-D float32 device tensor, got {tuple(cand.shape)} {cand.dtype}")
+    R, B = cand.shape
+    _check_softmax_state("softmax_merge", state, R)
+    cand, ld = _tile_view(cand)
+    nbytes = int(lib().sl_softmax_merge_ws_bytes(R, B))
+    if nbytes and (ws is None or ws.numel() < nbytes):
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=state.device)
+    with _on(state.device):
+        rc = lib().sl_softmax_merge(_ptr(state), R, _ptr(cand), ld, B, scale, _ptr(ws), nbytes, _stream(state))
+    _check(rc, "sl_softmax_merge")
+
+
+def softmax_finish(state: torch.Tensor, scale: float, vals: torch.Tensor | None = None):
+    """``(probs, log_z, entropy)`` of a state: ``log_z`` and ``entropy`` ``(R,)`` float64; ``probs (R, k)`` float32 =
+    ``exp(scale * vals - log_z)`` for K17's sorted ``vals (R, k)`` of the same candidates (0 for an empty slot), ``None`` without
+    ``vals``."""
+    scale = check_logit_scale(scale)
+    _check_softmax_state("softmax_finish", state)
+    R = state.shape[0]
+    probs, k = None, 0
+    if vals is not None:
+        if vals.ndim != 2 or vals.shape[0] != R or vals.dtype != torch.float32 or vals.device != state.device:
+            raise ValueError(f"softmax_finish: values {tuple(vals.shape)} {vals.dtype} do not fit a state of {R} rows")
+        vals = vals.contiguous()
+        k = check_topk_k(vals.shape[1])
+        probs = torch.empty((R, k), dtype=torch.float32, device=state.device)
+    log_z = torch.empty(R, dtype=torch.float64, device=state.device)
+    entropy = torch.empty(R, dtype=torch.float64, device=state.device)
+    with _on(state.device):
+        rc = lib().sl_softmax_finish(_ptr(state), R, scale, _ptr(vals), k, _ptr(probs), _ptr(log_z), _ptr(entropy), _stream(state))
+    _check(rc, "sl_softmax_finish")
+    return probs, log_z, entropy
+
+
+def softmax_probe(x: torch.Tensor, y: torch.Tensor, k: int, scale: float, chunk_rows: int | None = None, id_base: int = 0,
+                  state=None):
+    """``topk_probe`` with the softmax statistics of the same cosines: every tile the cosine GEMM writes is folded by K17 and then
+    by K25 on the same stream — one GEMM per tile, one reused tile buffer, one reused workspace.  Returns (and continues, as
+    ``state``) the triple ``(values (R, k), ids (R, k), softmax state (R, 4))``; ``values`` and ``ids`` are ``topk_probe``'s."""
+    k = check_topk_k(k)
+    scale = check_logit_scale(scale)
+    _check_probe_args("softmax_probe", x, y, chunk_rows=chunk_rows)
+    xd = _f32c(x)
+    yd = _f32c(y, xd.device)
+    R, n = xd.shape[0], yd.shape[0]
+    vals, ids, sm = state if state is not None else (*topk_new(R, k, xd.device), softmax_new(R, xd.device))
+    if R == 0 or n == 0:
+        return vals, ids, sm
+    step = min(chunk_rows or topk_chunk_rows(R, n), n)
+    tiles = _cosine_tiles(xd, yd, R, step)
+    # both kernels split a row by the same rule and the workspace grows with the tile's width: one buffer serves every merge
+    merge_bytes = max(int(lib().sl_topk_merge_ws_bytes(R, k, step)), int(lib().sl_softmax_merge_ws_bytes(R, step)))
+    merge_ws = torch.empty(merge_bytes, dtype=torch.uint8, device=xd.device) if merge_bytes else None
+    for _, _, c0, _, out in tiles:
+        topk_merge(vals, ids, out, id_base + c0, merge_ws)
+        softmax_merge(sm, out, scale, merge_ws)
+    return vals, ids, sm
 
 
 # ------------------------------------------------------------------------------------------------

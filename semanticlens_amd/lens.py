@@ -288,6 +288,92 @@ def label_components(fm, vocabulary: list[str], aggregated_concept_db, k: int = 
     return out if is_dict else out[None]
 
 
+# ------------------------------------------------------------------------------------------------
+# describe, calibrated: softmax over the whole vocabulary next to the top-k (K17 + K25 on the same tiles)
+# ------------------------------------------------------------------------------------------------
+@dataclass
+class LabelDistribution:
+    """What ``label_distribution`` returns for one layer: ``label_components``' top-k next to
+    ``softmax(logit_scale * cosine)`` taken over the WHOLE vocabulary.
+
+    * ``values`` / ``ids`` ``(C, k)``: ``label_components``' result, bit for bit.
+    * ``probs (C, k)`` float32: the probability of each returned label (0 in an empty slot, ``k > n_labels``).
+    * ``log_z`` / ``entropy`` ``(C,)`` float64: the log partition sum of ``logit_scale * cosine`` and the entropy in nats.
+
+    A component whose cosines hold a NaN has NaN everywhere; nothing filters it."""
+
+    values: torch.Tensor
+    ids: torch.Tensor
+    probs: torch.Tensor
+    log_z: torch.Tensor
+    entropy: torch.Tensor
+    n_labels: int
+    logit_scale: float
+
+    @property
+    def effective_labels(self) -> torch.Tensor:
+        """``exp(entropy)``: how many labels a component is really spread over, between 1 and ``n_labels``."""
+        return self.entropy.exp()
+
+    def confident(self, min_prob: float = 0.5) -> torch.Tensor:
+        """``(C,)`` bool: the best label holds at least ``min_prob``; ``False`` where the distribution is NaN."""
+        return self.probs[:, 0] >= min_prob
+
+
+@torch.no_grad()
+def probe_softmax(query_embeds: torch.Tensor, aggregated_concept_db, k: int, logit_scale: float = 100.0, chunk_rows: int | None = None):
+    """``probe_topk(per="component")`` with the softmax over ALL queries: per component
+    ``(values (C, k), ids (C, k), probs (C, k) float32, log_z (C,) float64, entropy (C,) float64)``, a dict of such tuples for a
+    dict DB.  ``values`` / ``ids`` are ``probe_topk``'s; ``probs[c, i] = exp(logit_scale * values[c, i] - log_z[c])`` where ``log_z``
+    is the log-sum-exp of ``logit_scale * cosine`` over every row of ``query_embeds``.  The ``(C, Q)`` matrix is never formed: K25
+    folds each tile K17 reads into a four-double state per component."""
+    k = N.check_topk_k(k)
+    scale = N.check_logit_scale(logit_scale)
+    if chunk_rows is not None and chunk_rows < 1:
+        raise ValueError(f"chunk_rows = {chunk_rows} must be at least 1")
+    names, layers, is_dict = _db_layers(aggregated_concept_db)
+    _check_width(query_embeds, layers)
+
+    def probe(ld, q):
+        vals, ids, sm = N.softmax_probe(ld, q, k, scale, chunk_rows)
+        return (vals, ids, *N.softmax_finish(sm, scale, vals))
+
+    return _probe_layers(names, layers, is_dict, query_embeds, probe)
+
+
+@torch.no_grad()
+def label_distribution(fm, vocabulary: list[str], aggregated_concept_db, k: int = 5, logit_scale: float = 100.0,
+                       templates: list[str] | None = None, batch_size: int | None = None, chunk_size: int | None = None):
+    """``label_components`` plus how much each label means: a ``LabelDistribution`` (a dict of them for a dict of layers) with the
+    same ``values`` / ``ids`` and, per component, ``softmax(logit_scale * cosine)`` over the whole vocabulary — the probability of
+    the ``k`` returned labels, the log partition sum and the entropy.  Raw cosines sit on a large common offset and cannot be
+    compared across components; ``probs[:, 0]`` and ``effective_labels`` can, and ``confident()`` says which components have a label
+    worth printing.  ``logit_scale``: the CLIP family trains with about 100.
+
+    Vocabulary, templates, ``batch_size``, ``chunk_size`` and what is checked before anything runs are ``label_components``'; the
+    softmax statistics are folded (K25) from the very tiles its top-k reads, so there is one GEMM per tile and no ``V x C`` matrix.
+    Chunking changes ``probs``, ``log_z`` and ``entropy`` only within the rounding bound of DESIGN.md §K25.
+
+    For a ``Facets`` pass ``facets.aggregated()``, as with ``audit_concepts``.  An empty facet's row is all zeros, its cosine to
+    every word is 0, so its distribution is uniform: ``probs = 1 / n_labels``, ``effective_labels = n_labels``."""
+    k = N.check_topk_k(k)
+    scale = N.check_logit_scale(logit_scale)
+    if isinstance(vocabulary, str) or not isinstance(vocabulary, (list, tuple)) or len(vocabulary) == 0:
+        raise ValueError("vocabulary must be a non-empty list of strings")
+    names, layers, is_dict = _db_layers(aggregated_concept_db)
+    chunks = _embedded_chunks(fm, list(vocabulary), layers, templates, batch_size, chunk_size)
+    dbs = [N._f32c(layer) for layer in layers]  # raises without a HIP device, before the text tower runs
+    states = [None] * len(dbs)
+    for start, _, embeds in chunks:
+        for i, db in enumerate(dbs):
+            states[i] = N.softmax_probe(db, embeds, k, scale, id_base=start, state=states[i])
+    out = {}
+    for name, layer, (vals, ids, sm) in zip(names, layers, states):
+        tensors = (vals, ids, *N.softmax_finish(sm, scale, vals))
+        out[name] = LabelDistribution(*(t.to(layer.device) for t in tensors), n_labels=len(vocabulary), logit_scale=scale)
+    return out if is_dict else out[None]
+
+
 @torch.no_grad()
 def search_components(fm, query, aggregated_concept_db, k: int = 10, templates: list[str] | None = None,
                       batch_size: int | None = None):
@@ -695,6 +781,10 @@ class Lens:
 
     def label_components(self, vocabulary, aggregated_concept_db, k=5, templates=None, batch_size=None, chunk_size=None):
         return label_components(self.fm, vocabulary, aggregated_concept_db, k, templates, batch_size, chunk_size)
+
+    def label_distribution(self, vocabulary, aggregated_concept_db, k=5, logit_scale=100.0, templates=None, batch_size=None,
+                           chunk_size=None):
+        return label_distribution(self.fm, vocabulary, aggregated_concept_db, k, logit_scale, templates, batch_size, chunk_size)
 
     def search_components(self, query, aggregated_concept_db, k=10, templates=None, batch_size=None):
         return search_components(self.fm, query, aggregated_concept_db, k, templates, batch_size)
