@@ -107,8 +107,10 @@ struct LinearEpi {
     if constexpr (ACT == SL_ACT_QUICKGELU) v = v * __builtin_amdgcn_rcpf(1.f + __expf(-1.702f * v));
     if constexpr (ACT == SL_ACT_GELU_TANH) {  // torch gelu(approximate="tanh"): SigLIP's "gelu_pytorch_tanh"
       const float u = 0.79788456080286535588f * __builtin_fmaf(0.044715f * v, v * v, v);
-      // 0.5 v (1 + tanh u) = v - v / (1 + exp(2 u)); exp overflow -> v, underflow -> 0
-      v = __builtin_fmaf(-v, __builtin_amdgcn_rcpf(1.f + __expf(2.f * u)), v);
+      // 0.5 v (1 + tanh u) = v - v / (1 + exp(2 u)); exp overflow -> v, underflow -> 0.  The overflow case is a select, not
+      // v - v * 0: the same bits for every finite v, and +inf stays +inf as in torch (inf * 0 made it NaN)
+      const float r = __builtin_amdgcn_rcpf(1.f + __expf(2.f * u));
+      v = r == 0.f ? v : __builtin_fmaf(-v, r, v);
     }
     const int64_t orow = out_row(row);
     if constexpr (REMAP) {
