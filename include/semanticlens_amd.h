@@ -596,6 +596,24 @@ size_t sl_softmax_merge_ws_bytes(int64_t R, int64_t B);
 int sl_softmax_finish(const double* d_state, int64_t R, double scale, const float* d_vals, int64_t k, float* d_probs,
                       double* d_log_z, double* d_entropy, void* stream);
 
+/* ---- K26: ranks of given keys among the candidates of cosine tiles — the count behind label_rank ----------
+ * No reference counterpart.  State: d_counts (R,T) int64, zero before the first tile.  A key is a (value, id) pair per row and slot:
+ * d_key_vals (R,T) fp32 and d_key_ids (R,T) int64, a negative id = unused slot.  A candidate (value, id) orders before a key iff
+ * its id differs from the key's and, in K17's order (NaN first, then the larger value, -0.0 == +0.0, equal values by the smaller
+ * id), it stands earlier: csrc/rank_order.hpp, host-checkable.  The candidate with the key's own id is never counted, so after
+ * every tile of a row was folded a count is the 0-based position the key holds in the sorted row.  Counts are integers: the state
+ * after a sequence of merges is the same whatever the cut into tiles, their order and the scheduling. */
+#define SL_RANK_MAX_TARGETS 16
+/* d_counts (R,T) int64 += per row r and slot t with d_key_ids[r*T+t] >= 0: the number of columns j in [0,B) for which
+ * orders_before(key(d_cand[r*ld+j]), id_base+j, key(d_key_vals[r*T+t]), d_key_ids[r*T+t]).  Slots with a negative key id are
+ * not touched.  The tile is read exactly as sl_topk_merge reads one: R rows of B >= 1 fp32 columns, row stride ld >= B elements,
+ * any 4-byte aligned start, nothing outside [0, B) of a row touched; id_base within [0, 2^62].  1 <= T <= SL_RANK_MAX_TARGETS;
+ * R == 0 is a no-op.  Few rows of many columns are split over sl_rank_merge_splits(R,B) wavefronts per row, whose partial counts
+ * are added with 64-bit integer atomics: no workspace. */
+int sl_rank_merge(int64_t* d_counts, int64_t R, int64_t T, const float* d_cand, int64_t ld, int64_t B, int64_t id_base,
+                  const float* d_key_vals, const int64_t* d_key_ids, void* stream);
+int64_t sl_rank_merge_splits(int64_t R, int64_t B); /* waves per row the launch uses; 1 for most shapes */
+
 /* normalize(x) @ normalize(y)^T for ANY shapes — x (M,K), y (N,K), out (M,N) — with K6's kernels and arithmetic mode
  * (sl_set_gemm_mode) and none of similarity_score's shape branches: what the tiled top-k probing calls per tile.
  * d_ws: sl_cosine_nt_ws_bytes(M,N,K) bytes. */
@@ -612,7 +630,7 @@ size_t sl_cosine_nt_ws_bytes(int64_t M, int64_t N, int64_t K);
 #define SL_PROF_GATHER 3
 #define SL_PROF_SCORES 4
 #define SL_PROF_BATCHNORM 5 /* K16 fused inference BatchNorm; launches = BatchNorm2d evaluations (K19) */
-#define SL_PROF_TOPK 6 /* K17 streaming fp32 top-k; K20 mutual best matches; K22 per-segment maxima; K24 redundancy groups */
+#define SL_PROF_TOPK 6 /* K17 streaming fp32 top-k; K20 mutual best matches; K22 per-segment maxima; K24 redundancy groups; K26 ranks */
 #define SL_PROF_SOFTMAX 7 /* K25 streaming softmax statistics */
 #define SL_PROF_NFAM 8
 int sl_prof_enable(int on);

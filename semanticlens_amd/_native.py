@@ -134,6 +134,8 @@ SIGNATURES = {
     "sl_softmax_merge": (_int, [_vp, _i64, _vp, _i64, _i64, ctypes.c_double, _vp, _sz, _vp]),
     "sl_softmax_merge_ws_bytes": (_sz, [_i64, _i64]),
     "sl_softmax_finish": (_int, [_vp, _i64, ctypes.c_double, _vp, _i64, _vp, _vp, _vp, _vp]),
+    "sl_rank_merge": (_int, [_vp, _i64, _i64, _vp, _i64, _i64, _i64, _vp, _vp, _vp]),
+    "sl_rank_merge_splits": (_i64, [_i64, _i64]),
     "sl_mutualmax_merge": (_int, [_vp, _vp, _i64, _i64, _vp, _i64, _i64, _i64, _vp]),
     "sl_mutualmax_finish": (_int, [_vp, _i64, _vp, _vp, _vp]),
     "sl_segmax_merge": (_int, [_vp, _i64, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _vp]),
@@ -1090,6 +1092,146 @@ def softmax_probe(x: torch.Tensor, y: torch.Tensor, k: int, scale: float, chunk_
         softmax_merge(sm, out, scale, merge_ws)
     return vals, ids, sm
 
+
+# ------------------------------------------------------------------------------------------------
+# K26: ranks of given keys among the candidates of the same cosine tiles
+# ------------------------------------------------------------------------------------------------
+RANK_MAX_TARGETS = 16  # key slots per row (include/semanticlens_amd.h: SL_RANK_MAX_TARGETS)
+
+
+def check_rank_targets(targets, R: int, n: int) -> torch.Tensor:
+    """``targets`` as an ``(R, T)`` int64 CPU tensor, ``T`` the longest row (at least 1), rows padded with -1 = unused slot.  Per
+    row: an int, ``None`` / -1 (no target), or a list of up to ``RANK_MAX_TARGETS`` ints, each in ``[0, n)`` or -1; a tensor or
+    array of one or two dimensions is read as its ``tolist()``.  Anything else is a ``ValueError``."""
+    if hasattr(targets, "tolist"):
+        t = torch.as_tensor(targets)
+        if t.ndim in (1, 2) and t.numel() and not t.dtype.is_floating_point and not t.dtype.is_complex and t.dtype != torch.bool:
+            t = t.to("cpu", torch.int64).reshape(t.shape[0], -1)  # the whole array at once: no Python loop over the rows
+            if t.shape[0] != R:
+                raise ValueError(f"targets has {t.shape[0]} entries for {R} rows")
+            if t.shape[1] > RANK_MAX_TARGETS:
+                raise ValueError(f"targets holds {t.shape[1]} targets per row, more than {RANK_MAX_TARGETS}")
+            if int(t.min()) < -1 or int(t.max()) >= n:
+                raise ValueError(f"targets: an index lies outside [0, {n}) (-1 = no target)")
+            return t.clone().contiguous()
+        targets = targets.tolist()
+    if isinstance(targets, (str, bytes)) or not isinstance(targets, (list, tuple)):
+        raise ValueError(f"targets must be a sequence with one entry per row, got {type(targets).__name__}")
+    if len(targets) != R:
+        raise ValueError(f"targets has {len(targets)} entries for {R} rows")
+    rows = []
+    for r, entry in enumerate(targets):
+        if hasattr(entry, "tolist"):
+            entry = entry.tolist()
+        items = list(entry) if isinstance(entry, (list, tuple)) else [entry]
+        if len(items) > RANK_MAX_TARGETS:
+            raise ValueError(f"targets[{r}] holds {len(items)} targets, more than {RANK_MAX_TARGETS}")
+        row = []
+        for item in items:
+            if item is None:
+                item = -1
+            try:
+                if isinstance(item, bool):
+                    raise TypeError
+                item = operator.index(item)
+            except TypeError:
+                raise ValueError(f"targets[{r}]: {item!r} is not an index") from None
+            if not -1 <= item < n:
+                raise ValueError(f"targets[{r}]: index {item} outside [0, {n}) (-1 = no target)")
+            row.append(item)
+        rows.append(row)
+    T = max([1] + [len(row) for row in rows])
+    out = torch.full((R, T), -1, dtype=torch.int64)
+    for r, row in enumerate(rows):
+        if row:
+            out[r, : len(row)] = torch.tensor(row, dtype=torch.int64)
+    return out
+
+
+def _check_rank_state(what: str, counts: torch.Tensor, key_vals: torch.Tensor, key_ids: torch.Tensor, R: int | None = None):
+    if (counts.ndim != 2 or counts.dtype != torch.int64 or not counts.is_cuda or not counts.is_contiguous()
+            or not 1 <= counts.shape[1] <= RANK_MAX_TARGETS):
+        raise ValueError(f"{what}: counts are a contiguous (R, T) int64 device tensor with T in [1, {RANK_MAX_TARGETS}], got "
+                         f"{tuple(counts.shape)} {counts.dtype} on {counts.device}")
+    for name, t, dtype in (("key values", key_vals, torch.float32), ("key ids", key_ids, torch.int64)):
+        if t.shape != counts.shape or t.dtype != dtype or t.device != counts.device or not t.is_contiguous():
+            raise ValueError(f"{what}: {name} must be a contiguous {tuple(counts.shape)} {dtype} tensor on {counts.device}, got "
+                             f"{tuple(t.shape)} {t.dtype} on {t.device}")
+    if R is not None and counts.shape[0] != R:
+        raise ValueError(f"{what}: counts of {counts.shape[0]} rows do not fit {R}")
+
+
+def rank_merge(counts: torch.Tensor, cand: torch.Tensor, key_vals: torch.Tensor, key_ids: torch.Tensor, id_base: int = 0):
+    """Per row and slot with ``key_ids >= 0``: ``counts (R, T) int64 +=`` the number of columns of the ``(R, B)`` fp32 tile ``cand`` (unit
+    column stride, any row stride; column ``j`` has the id ``id_base + j``) that order before the key ``(key_vals, key_ids)`` in K17's
+    order; the key's own column is never counted (K26, csrc/rank_order.hpp)."""
+    if cand.ndim != 2 or cand.dtype != torch.float32 or not cand.is_cuda:
+        raise ValueError(f"rank_merge: the candidate tile must be a 2-D float32 device tensor, got {tuple(cand.shape)} {cand.dtype}")
+    R, B = cand.shape
+    _check_rank_state("rank_merge", counts, key_vals, key_ids, R)
+    cand, ld = _tile_view(cand)
+    with _on(counts.device):
+        rc = lib().sl_rank_merge(_ptr(counts), R, counts.shape[1], _ptr(cand), ld, B, id_base, _ptr(key_vals), _ptr(key_ids),
+                                 _stream(counts))
+    _check(rc, "sl_rank_merge")
+
+
+def rank_keys(x: torch.Tensor, y: torch.Tensor, targets: torch.Tensor, chunk_rows: int | None = None) -> torch.Tensor:
+    """``(R, T)`` float32: the cosine of row ``r`` of ``x (R, D)`` to row ``targets[r, t]`` of ``y (n, D)``, NaN where ``targets`` is
+    negative.  The values come out of the cosine GEMM (K6) — the unique target rows of ``y`` as the columns of the tiles
+    ``topk_probe`` walks — so they are computed in the arithmetic mode and from the operand preparation of the tiles they will be
+    compared with; two K6 calls differ by the accumulation order at most."""
+    _check_probe_args("rank_keys", x, y, chunk_rows=chunk_rows)
+    if targets.ndim != 2 or targets.shape[0] != x.shape[0] or targets.dtype != torch.int64:
+        raise ValueError(f"rank_keys: targets {tuple(targets.shape)} {targets.dtype} are not (R, T) int64 for {x.shape[0]} rows")
+    if targets.numel() and not (-1 <= int(targets.min()) and int(targets.max()) < y.shape[0]):
+        raise ValueError(f"rank_keys: a target lies outside [0, {y.shape[0]}) (-1 = no target)")
+    used = targets >= 0
+    nothing = not bool(used.any())
+    xd = _f32c(x)
+    R = xd.shape[0]
+    vals = torch.full(targets.shape, float("nan"), dtype=torch.float32, device=xd.device)
+    if R == 0 or nothing:
+        return vals
+    uniq = torch.unique(targets[used])  # sorted
+    pos = torch.searchsorted(uniq, targets.clamp(min=0)).to(xd.device)  # the column of yu that holds targets[r, t]
+    used = used.to(xd.device)
+    yu = _f32c(y[uniq.to(y.device)], xd.device)
+    U = yu.shape[0]
+    step = min(chunk_rows or topk_chunk_rows(R, U), U)
+    for _, _, c0, nc, out in _cosine_tiles(xd, yu, R, step):
+        here = used & (pos >= c0) & (pos < c0 + nc)
+        vals = torch.where(here, out.gather(1, (pos - c0).clamp(0, nc - 1)), vals)
+    return vals
+
+
+def rank_probe(x: torch.Tensor, y: torch.Tensor, key_vals: torch.Tensor, key_ids: torch.Tensor, chunk_rows: int | None = None,
+               id_base: int = 0, state: torch.Tensor | None = None, softmax=None) -> torch.Tensor:
+    """``topk_probe``'s walk with K26 as the fold: per row of ``x (R, D)`` and key slot, the number of rows of ``y (N, D)`` (row ``j``
+    has the id ``id_base + j``) whose cosine orders before the key ``(key_vals, key_ids) (R, T)``.  Returns (and continues, as
+    ``state``) the ``(R, T)`` int64 counts; slots with a negative key id stay as they are.  ``softmax=(state, scale)``: K25 folds the
+    same tiles into that ``(R, 4)`` softmax state, as ``softmax_probe`` does."""
+    _check_probe_args("rank_probe", x, y, chunk_rows=chunk_rows)
+    xd = _f32c(x)
+    yd = _f32c(y, xd.device)
+    R, n = xd.shape[0], yd.shape[0]
+    counts = state if state is not None else torch.zeros(key_ids.shape, dtype=torch.int64, device=xd.device)
+    _check_rank_state("rank_probe", counts, key_vals, key_ids, R)
+    sm, scale = softmax if softmax is not None else (None, None)
+    if sm is not None:
+        scale = check_logit_scale(scale)
+        _check_softmax_state("rank_probe", sm, R)
+    if R == 0 or n == 0:
+        return counts
+    step = min(chunk_rows or topk_chunk_rows(R, n), n)
+    tiles = _cosine_tiles(xd, yd, R, step)
+    merge_bytes = int(lib().sl_softmax_merge_ws_bytes(R, step)) if sm is not None else 0
+    merge_ws = torch.empty(merge_bytes, dtype=torch.uint8, device=xd.device) if merge_bytes else None
+    for _, _, c0, _, out in tiles:
+        rank_merge(counts, out, key_vals, key_ids, id_base + c0)
+        if sm is not None:
+            softmax_merge(sm, out, scale, merge_ws)
+    return counts
 
 # ------------------------------------------------------------------------------------------------
 # K20: mutual best matches (row and column maxima of every cosine tile in one read)

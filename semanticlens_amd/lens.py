@@ -374,6 +374,194 @@ def label_distribution(fm, vocabulary: list[str], aggregated_concept_db, k: int 
     return out if is_dict else out[None]
 
 
+# ------------------------------------------------------------------------------------------------
+# describe, evaluated: where an expected label stands among all V words (K26 on the tiles K17 reads)
+# ------------------------------------------------------------------------------------------------
+@dataclass
+class LabelRanks:
+    """What ``label_rank`` / ``probe_rank`` return for one layer: per component and target slot, the position the target holds
+    when the component's cosines to all ``n_labels`` words are sorted in ``label_components``' order.
+
+    * ``rank (C, T)`` int64: 0 = the target is the top label; -1 in an unused slot.
+    * ``value (C, T)`` float32: the target's cosine; NaN in an unused slot.
+    * ``targets (C, T)`` int64: the vocabulary indices asked for, -1 = unused.
+    * ``prob (C, T)`` float32 = ``exp(logit_scale * value - log_z)`` and ``log_z (C,)`` float64, the log partition sum over the
+      whole vocabulary (``label_distribution``'s); both ``None`` without a ``logit_scale``.
+
+    A target is *valid* when it is used and its cosine is not NaN.  ``rank`` follows the order as it is — a NaN target ranks
+    first, as it would in ``label_components`` — while ``best``, ``hit`` and the metrics leave NaN targets out."""
+
+    rank: torch.Tensor
+    value: torch.Tensor
+    targets: torch.Tensor
+    prob: torch.Tensor | None
+    log_z: torch.Tensor | None
+    n_labels: int
+    logit_scale: float | None = None
+
+    def _valid(self) -> torch.Tensor:
+        return (self.targets >= 0) & ~self.value.isnan()
+
+    def best(self) -> torch.Tensor:
+        """``(C,)`` int64: the smallest rank over the component's valid targets (synonyms), -1 without one."""
+        valid = self._valid()
+        best = self.rank.masked_fill(~valid, torch.iinfo(torch.int64).max).amin(dim=1)
+        return best.masked_fill(~valid.any(dim=1), -1)
+
+    def hit(self, k: int) -> torch.Tensor:
+        """``(C,)`` bool: a valid target is among the component's ``k`` best labels."""
+        best = self.best()
+        return (best >= 0) & (best < k)
+
+    @property
+    def n_evaluated(self) -> int:
+        """The number of components with at least one valid target: what the metrics average over."""
+        return int(self._valid().any(dim=1).sum())
+
+    def topk_accuracy(self, k: int) -> float:
+        """The share of evaluated components with ``hit(k)``; NaN when none is evaluated."""
+        n = self.n_evaluated
+        return float(self.hit(k).sum()) / n if n else float("nan")
+
+    def mrr(self) -> float:
+        """Mean reciprocal rank ``1 / (best() + 1)`` over the evaluated components; NaN when none is evaluated."""
+        best = self.best()
+        best = best[best >= 0]
+        return float((1.0 / (best.double() + 1.0)).mean()) if best.numel() else float("nan")
+
+
+def _rank_layers(aggregated_concept_db, targets):
+    """``(names, layers, is_dict, per-layer targets)`` for the layers ``targets`` names: all of a tensor DB, a subset of a dict DB."""
+    names, layers, is_dict = _db_layers(aggregated_concept_db)
+    if not is_dict:
+        if isinstance(targets, Mapping):
+            raise ValueError("targets is a dict but the concept DB is a single tensor")
+        return names, layers, is_dict, [targets]
+    if not isinstance(targets, Mapping):
+        raise ValueError("for a dict of layers, targets must be a dict over (a subset of) its layer names")
+    unknown = [name for name in targets if name not in aggregated_concept_db]
+    if unknown:
+        raise ValueError(f"targets names unknown layers {unknown}; the concept DB has {names}")
+    keep = [i for i, name in enumerate(names) if name in targets]
+    return [names[i] for i in keep], [layers[i] for i in keep], is_dict, [targets[names[i]] for i in keep]
+
+
+def _resolve_targets(targets, n_components: int, n_labels: int, vocabulary=None, index=None) -> torch.Tensor:
+    """One layer's targets as ``N.check_rank_targets``' ``(C, T)`` tensor; words are looked up in ``vocabulary`` (first occurrence,
+    through ``index``, a dict the caller keeps across layers)."""
+    if hasattr(targets, "tolist"):  # a tensor or an array holds indices only
+        return N.check_rank_targets(targets, n_components, n_labels)
+    if isinstance(targets, (str, bytes)) or not isinstance(targets, (list, tuple)):
+        raise ValueError(f"targets must hold one entry per component, got {type(targets).__name__}")
+
+    def lookup(item):
+        if not isinstance(item, str):
+            return item
+        if vocabulary is None:
+            raise ValueError(f"target {item!r} is a word, but there is no vocabulary to look it up in: pass indices")
+        if not index:
+            for i, word in enumerate(vocabulary):
+                index.setdefault(word, i)
+        if item not in index:
+            raise ValueError(f"target word {item!r} is not in the vocabulary")
+        return index[item]
+
+    resolved = [[lookup(i) for i in entry] if isinstance(entry, (list, tuple)) else lookup(entry) for entry in targets]
+    return N.check_rank_targets(resolved, n_components, n_labels)
+
+
+def _rank_result(layer, targets, key_vals, counts, sm, scale, n_labels: int) -> LabelRanks:
+    used = targets >= 0
+    rank = counts.masked_fill(~used, -1)
+    prob = log_z = None
+    if sm is not None:
+        _, log_z, _ = N.softmax_finish(sm, scale)
+        prob = (scale * key_vals.double() - log_z[:, None]).exp().float()
+    dev = layer.device
+    return LabelRanks(rank.to(dev), key_vals.to(dev), targets.to(dev), None if prob is None else prob.to(dev),
+                      None if log_z is None else log_z.to(dev), n_labels, scale)
+
+
+@torch.no_grad()
+def probe_rank(query_embeds: torch.Tensor, aggregated_concept_db, targets, chunk_rows: int | None = None,
+               logit_scale: float | None = None):
+    """For every component, where expected queries stand among ALL rows of ``query_embeds (Q, D)``: a ``LabelRanks`` (a dict of
+    them for a dict DB), for callers who bring their own vectors.  ``targets``: per component a row index of ``query_embeds``, a
+    list of up to 16 of them, or ``None``; for a dict DB a dict over a subset of its layers, and only those are ranked.
+
+    ``rank[c, t]`` is the number of queries that ``probe_topk(per="component")`` would list before the target: given the targets'
+    cosines and the tiles' cosines it is exact, and ``rank[c, t] < k`` can disagree with membership in ``probe_topk``'s ids, or with
+    the float64 rank, only by candidates whose cosine lies within the cosine GEMM's rounding of the target's.  The ``(C, Q)`` matrix
+    is never formed: the targets' cosines are taken through the same GEMM first, then K26 counts, per tile K17 would read, the
+    candidates that order before them.  With ``logit_scale``, K25 folds the same tiles and ``prob`` / ``log_z`` are filled."""
+    scale = None if logit_scale is None else N.check_logit_scale(logit_scale)
+    if chunk_rows is not None and chunk_rows < 1:
+        raise ValueError(f"chunk_rows = {chunk_rows} must be at least 1")
+    names, layers, is_dict, per_layer = _rank_layers(aggregated_concept_db, targets)
+    _check_width(query_embeds, layers)
+    n = query_embeds.shape[0]
+    resolved = [_resolve_targets(t, layer.shape[0], n) for t, layer in zip(per_layer, layers)]
+    out, q = {}, None
+    for name, layer, tg in zip(names, layers, resolved):
+        db = N._f32c(layer)
+        q = N._f32c(query_embeds, db.device) if q is None or q.device != db.device else q
+        key_vals = N.rank_keys(db, q, tg, chunk_rows)  # the targets are still on the host: its checks cost no readback
+        tg = tg.to(db.device)
+        sm = N.softmax_new(db.shape[0], db.device) if scale is not None else None
+        counts = N.rank_probe(db, q, key_vals, tg, chunk_rows, softmax=None if sm is None else (sm, scale))
+        out[name] = _rank_result(layer, tg, key_vals, counts, sm, scale, n)
+    return out if is_dict else out[None]
+
+
+@torch.no_grad()
+def label_rank(fm, vocabulary: list[str], aggregated_concept_db, targets, templates: list[str] | None = None,
+               batch_size: int | None = None, chunk_size: int | None = None, logit_scale: float | None = None):
+    """For labels you expect, where they stand among all of ``vocabulary``: a ``LabelRanks`` (a dict of them for a dict of layers)
+    whose ``rank[c, t]`` is the 0-based position of target ``t`` in the list ``label_components`` would return for component ``c``
+    with ``k = len(vocabulary)`` — the number a labelling is evaluated with (``hit``, ``topk_accuracy``, ``mrr``).
+
+    ``targets``: per component a vocabulary index, a word (looked up in ``vocabulary``, first occurrence; an absent word is a
+    ``ValueError``), a list of up to 16 of either (synonyms), or ``None``.  For a dict DB a dict over a subset of its layers: only
+    those layers are ranked and returned.
+
+    The unique target words are embedded first, with the same templates as the vocabulary, and their cosines taken through the
+    cosine GEMM; then the vocabulary is streamed exactly as ``label_components`` streams it and K26 counts, per tile, the words
+    that order before each target.  Neither the ``V x C`` matrix nor, for ``chunk_size < V``, all embeddings are ever resident; the
+    target words are embedded twice.  Given the targets' cosines and the tiles' cosines the rank is exact; it can differ from
+    the float64 rank, and ``rank < k`` from membership in ``label_components``' ids, only by words whose cosine lies within the
+    cosine GEMM's rounding of the target's.  With ``logit_scale``, ``prob`` / ``log_z`` are ``label_distribution``'s softmax over the
+    whole vocabulary (K25 on the same tiles).  Arguments are checked before anything runs, as in ``label_components``."""
+    scale = None if logit_scale is None else N.check_logit_scale(logit_scale)
+    if isinstance(vocabulary, str) or not isinstance(vocabulary, (list, tuple)) or len(vocabulary) == 0:
+        raise ValueError("vocabulary must be a non-empty list of strings")
+    vocabulary = list(vocabulary)
+    names, layers, is_dict, per_layer = _rank_layers(aggregated_concept_db, targets)
+    index = {}
+    resolved = [_resolve_targets(t, layer.shape[0], len(vocabulary), vocabulary, index) for t, layer in zip(per_layer, layers)]
+    chunks = _embedded_chunks(fm, vocabulary, layers, templates, batch_size, chunk_size)
+    dbs = [N._f32c(layer) for layer in layers]  # raises without a HIP device, before the text tower runs
+    # the targets' cosines: the unique target words of all layers, embedded once
+    uniq = torch.unique(torch.cat([t[t >= 0] for t in resolved])) if resolved else torch.empty(0, dtype=torch.int64)
+    key_ids = [t.to(db.device) for t, db in zip(resolved, dbs)]
+    if uniq.numel():
+        embeds = _embed_words(fm, [vocabulary[i] for i in uniq.tolist()], templates, batch_size)
+        _check_width(embeds, layers)
+        key_vals = [N.rank_keys(db, embeds, torch.searchsorted(uniq, t.clamp(min=0)).masked_fill(t < 0, -1))
+                    for db, t in zip(dbs, resolved)]
+        del embeds
+    else:
+        key_vals = [torch.full(t.shape, float("nan"), dtype=torch.float32, device=t.device) for t in key_ids]
+    counts = [None] * len(dbs)
+    sms = [N.softmax_new(db.shape[0], db.device) if scale is not None else None for db in dbs]
+    for start, _, embeds in chunks:
+        for i, db in enumerate(dbs):
+            counts[i] = N.rank_probe(db, embeds, key_vals[i], key_ids[i], id_base=start, state=counts[i],
+                                     softmax=None if sms[i] is None else (sms[i], scale))
+    out = {name: _rank_result(layer, key_ids[i], key_vals[i], counts[i], sms[i], scale, len(vocabulary))
+           for i, (name, layer) in enumerate(zip(names, layers))}
+    return out if is_dict else out[None]
+
+
 @torch.no_grad()
 def search_components(fm, query, aggregated_concept_db, k: int = 10, templates: list[str] | None = None,
                       batch_size: int | None = None):
@@ -785,6 +973,9 @@ class Lens:
     def label_distribution(self, vocabulary, aggregated_concept_db, k=5, logit_scale=100.0, templates=None, batch_size=None,
                            chunk_size=None):
         return label_distribution(self.fm, vocabulary, aggregated_concept_db, k, logit_scale, templates, batch_size, chunk_size)
+
+    def label_rank(self, vocabulary, aggregated_concept_db, targets, templates=None, batch_size=None, chunk_size=None, logit_scale=None):
+        return label_rank(self.fm, vocabulary, aggregated_concept_db, targets, templates, batch_size, chunk_size, logit_scale)
 
     def search_components(self, query, aggregated_concept_db, k=10, templates=None, batch_size=None):
         return search_components(self.fm, query, aggregated_concept_db, k, templates, batch_size)
