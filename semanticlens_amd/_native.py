@@ -11,6 +11,7 @@ import ctypes
 import math
 import operator
 import os
+from collections import namedtuple
 from pathlib import Path
 
 import torch
@@ -874,17 +875,33 @@ def _tile_view(cand: torch.Tensor) -> tuple[torch.Tensor, int]:
     return cand, ld
 
 
+def _check_cand_tile(what: str, cand: torch.Tensor, device=None, rows: int | None = None):
+    """What every merge refuses first: a candidate tile that is not 2-D float32 on ``device`` (any HIP device when ``None``), or
+    not of ``rows`` rows."""
+    if cand.ndim != 2 or cand.dtype != torch.float32 or (not cand.is_cuda if device is None else cand.device != device):
+        where = "device tensor" if device is None else f"tensor on {device}"
+        raise ValueError(f"{what}: the candidate tile must be a 2-D float32 {where}, got {tuple(cand.shape)} {cand.dtype} on "
+                         f"{cand.device}")
+    if rows is not None and cand.shape[0] != rows:
+        raise ValueError(f"{what}: candidate tile {tuple(cand.shape)} {cand.dtype} does not fit a state of {rows} rows")
+
+
+def _ws_for(nbytes: int, ws: torch.Tensor | None, device) -> torch.Tensor | None:
+    """``ws`` where it holds ``nbytes``, else a new uint8 buffer of that size on ``device``; ``nbytes == 0`` allocates nothing."""
+    if nbytes and (ws is None or ws.numel() < nbytes):
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=device)
+    return ws
+
+
 def topk_merge(vals: torch.Tensor, ids: torch.Tensor, cand: torch.Tensor, id_base: int = 0, ws: torch.Tensor | None = None):
     """Fold the ``(R, B)`` fp32 tile ``cand`` (unit column stride, any row stride) into the state; column ``j`` has the id
     ``id_base + j``.  ``ws``: a uint8 device buffer to use as the workspace of a split row when it is large enough."""
     R, k = vals.shape
-    if cand.ndim != 2 or cand.shape[0] != R or cand.dtype != torch.float32 or not cand.is_cuda:
-        raise ValueError(f"topk_merge: candidate tile {tuple(cand.shape)} {cand.dtype} does not fit a state of {R} rows")
+    _check_cand_tile("topk_merge", cand, rows=R)
     B = cand.shape[1]
     cand, ld = _tile_view(cand)
     nbytes = int(lib().sl_topk_merge_ws_bytes(R, k, B))
-    if nbytes and (ws is None or ws.numel() < nbytes):
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=vals.device)
+    ws = _ws_for(nbytes, ws, vals.device)
     with _on(vals.device):
         rc = lib().sl_topk_merge(_ptr(vals), _ptr(ids), R, k, _ptr(cand), ld, B, id_base, _ptr(ws), nbytes, _stream(vals))
     _check(rc, "sl_topk_merge")
@@ -964,6 +981,45 @@ def _cosine_tiles(xd: torch.Tensor, yd: torch.Tensor, rows: int, cols: int, walk
     return tiles()
 
 
+def _row_tiles(xd: torch.Tensor, yd: torch.Tensor, chunk_rows: int | None):
+    """``(step, tiles)`` of the row probes' walk: ``_cosine_tiles`` over tiles of all ``R`` rows of ``xd`` (the walk's single-row-block
+    case) by ``step`` rows of ``yd`` — ``chunk_rows``, by default ``topk_chunk_rows``' — the last tile narrower."""
+    R, n = xd.shape[0], yd.shape[0]
+    step = min(chunk_rows or topk_chunk_rows(R, n), n)
+    return step, _cosine_tiles(xd, yd, R, step)
+
+
+# A consumer of the row probes' tiles: ``ws_bytes(R, step)`` is the split-row workspace its merge of an ``(R, step)`` tile needs,
+# ``merge(out, c0, ws)`` folds the tile ``out`` whose first column is row ``c0`` of ``y``.
+_Fold = namedtuple("_Fold", "ws_bytes merge")
+
+
+def _row_probe(fn: str, x: torch.Tensor, y: torch.Tensor, chunk_rows: int | None, setup):
+    """The walk of ``topk_probe``, ``softmax_probe`` and ``rank_probe``.  Checks the arguments, brings both operands to the device
+    and calls ``setup(R, device)``, which makes (or checks) the caller's state and gives ``(result, [fold, ...])``; returns
+    ``result``.  Unless an operand is empty, each tile the cosine GEMM (K6) writes is folded by every ``_Fold`` in list order on the
+    same stream.  The tile buffer and ONE merge workspace are allocated before the first tile: all kernels split a row by one
+    rule (csrc/rowseg_tile.hpp) and the workspace grows with the tile's width, so the largest fold's serves every merge."""
+    _check_probe_args(fn, x, y, chunk_rows=chunk_rows)
+    xd = _f32c(x)
+    yd = _f32c(y, xd.device)
+    R, n = xd.shape[0], yd.shape[0]
+    result, folds = setup(R, xd.device)
+    if R == 0 or n == 0:
+        return result
+    step, tiles = _row_tiles(xd, yd, chunk_rows)
+    merge_ws = _ws_for(max(int(fold.ws_bytes(R, step)) for fold in folds), None, xd.device)
+    for _, _, c0, _, out in tiles:
+        for fold in folds:
+            fold.merge(out, c0, merge_ws)
+    return result
+
+
+def _topk_fold(vals: torch.Tensor, ids: torch.Tensor, id_base: int):
+    return _Fold(lambda R, step: lib().sl_topk_merge_ws_bytes(R, vals.shape[1], step),
+                 lambda out, c0, ws: topk_merge(vals, ids, out, id_base + c0, ws))
+
+
 def topk_probe(x: torch.Tensor, y: torch.Tensor, k: int, chunk_rows: int | None = None, id_base: int = 0, state=None):
     """Per row of ``x (R, D)``: the ``k`` largest cosines against the rows of ``y (N, D)`` (row ``j`` has the id
     ``id_base + j``), as ``(values (R, k) float32, ids (R, k) int64)``.
@@ -972,21 +1028,12 @@ def topk_probe(x: torch.Tensor, y: torch.Tensor, k: int, chunk_rows: int | None 
     the arithmetic ``set_gemm_mode`` selects) writes one reused ``(R, chunk_rows)`` tile at a time and K17 folds it into the
     state on the same stream, so the ``(R, N)`` matrix never exists.  ``state``: continue an existing ``(values, ids)`` pair."""
     k = check_topk_k(k)
-    _check_probe_args("topk_probe", x, y, chunk_rows=chunk_rows)
-    xd = _f32c(x)
-    yd = _f32c(y, xd.device)
-    R, n = xd.shape[0], yd.shape[0]
-    vals, ids = state if state is not None else topk_new(R, k, xd.device)
-    if R == 0 or n == 0:
-        return vals, ids
-    step = min(chunk_rows or topk_chunk_rows(R, n), n)  # a tile spans all of x: the walk's single-row-block case
-    tiles = _cosine_tiles(xd, yd, R, step)
-    # the split-row workspace is largest for the widest tile (the waves per row grow with the columns), so one buffer serves all
-    merge_bytes = int(lib().sl_topk_merge_ws_bytes(R, k, step))
-    merge_ws = torch.empty(merge_bytes, dtype=torch.uint8, device=xd.device) if merge_bytes else None
-    for _, _, c0, _, out in tiles:
-        topk_merge(vals, ids, out, id_base + c0, merge_ws)
-    return vals, ids
+
+    def setup(R, device):
+        vals, ids = state if state is not None else topk_new(R, k, device)
+        return (vals, ids), [_topk_fold(vals, ids, id_base)]
+
+    return _row_probe("topk_probe", x, y, chunk_rows, setup)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -1033,14 +1080,12 @@ def softmax_merge(state: torch.Tensor, cand: torch.Tensor, scale: float, ws: tor
     """Fold the ``(R, B)`` fp32 tile ``cand`` (unit column stride, any row stride), as logits ``scale * cand``, into the state.
     ``ws``: a uint8 device buffer to use as the workspace of a split row when it is large enough."""
     scale = check_logit_scale(scale)
-    if cand.ndim != 2 or cand.dtype != torch.float32 or not cand.is_cuda:
-        raise ValueError(f"softmax_merge: the candidate tile must be a 2-D float32 device tensor, got {tuple(cand.shape)} {cand.dtype}")
+    _check_cand_tile("softmax_merge", cand)
     R, B = cand.shape
     _check_softmax_state("softmax_merge", state, R)
     cand, ld = _tile_view(cand)
     nbytes = int(lib().sl_softmax_merge_ws_bytes(R, B))
-    if nbytes and (ws is None or ws.numel() < nbytes):
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=state.device)
+    ws = _ws_for(nbytes, ws, state.device)
     with _on(state.device):
         rc = lib().sl_softmax_merge(_ptr(state), R, _ptr(cand), ld, B, scale, _ptr(ws), nbytes, _stream(state))
     _check(rc, "sl_softmax_merge")
@@ -1068,6 +1113,10 @@ def softmax_finish(state: torch.Tensor, scale: float, vals: torch.Tensor | None 
     return probs, log_z, entropy
 
 
+def _softmax_fold(sm: torch.Tensor, scale: float):
+    return _Fold(lambda R, step: lib().sl_softmax_merge_ws_bytes(R, step), lambda out, c0, ws: softmax_merge(sm, out, scale, ws))
+
+
 def softmax_probe(x: torch.Tensor, y: torch.Tensor, k: int, scale: float, chunk_rows: int | None = None, id_base: int = 0,
                   state=None):
     """``topk_probe`` with the softmax statistics of the same cosines: every tile the cosine GEMM writes is folded by K17 and then
@@ -1075,22 +1124,12 @@ def softmax_probe(x: torch.Tensor, y: torch.Tensor, k: int, scale: float, chunk_
     ``state``) the triple ``(values (R, k), ids (R, k), softmax state (R, 4))``; ``values`` and ``ids`` are ``topk_probe``'s."""
     k = check_topk_k(k)
     scale = check_logit_scale(scale)
-    _check_probe_args("softmax_probe", x, y, chunk_rows=chunk_rows)
-    xd = _f32c(x)
-    yd = _f32c(y, xd.device)
-    R, n = xd.shape[0], yd.shape[0]
-    vals, ids, sm = state if state is not None else (*topk_new(R, k, xd.device), softmax_new(R, xd.device))
-    if R == 0 or n == 0:
-        return vals, ids, sm
-    step = min(chunk_rows or topk_chunk_rows(R, n), n)
-    tiles = _cosine_tiles(xd, yd, R, step)
-    # both kernels split a row by the same rule and the workspace grows with the tile's width: one buffer serves every merge
-    merge_bytes = max(int(lib().sl_topk_merge_ws_bytes(R, k, step)), int(lib().sl_softmax_merge_ws_bytes(R, step)))
-    merge_ws = torch.empty(merge_bytes, dtype=torch.uint8, device=xd.device) if merge_bytes else None
-    for _, _, c0, _, out in tiles:
-        topk_merge(vals, ids, out, id_base + c0, merge_ws)
-        softmax_merge(sm, out, scale, merge_ws)
-    return vals, ids, sm
+
+    def setup(R, device):
+        vals, ids, sm = state if state is not None else (*topk_new(R, k, device), softmax_new(R, device))
+        return (vals, ids, sm), [_topk_fold(vals, ids, id_base), _softmax_fold(sm, scale)]
+
+    return _row_probe("softmax_probe", x, y, chunk_rows, setup)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -1165,8 +1204,7 @@ def rank_merge(counts: torch.Tensor, cand: torch.Tensor, key_vals: torch.Tensor,
     """Per row and slot with ``key_ids >= 0``: ``counts (R, T) int64 +=`` the number of columns of the ``(R, B)`` fp32 tile ``cand`` (unit
     column stride, any row stride; column ``j`` has the id ``id_base + j``) that order before the key ``(key_vals, key_ids)`` in K17's
     order; the key's own column is never counted (K26, csrc/rank_order.hpp)."""
-    if cand.ndim != 2 or cand.dtype != torch.float32 or not cand.is_cuda:
-        raise ValueError(f"rank_merge: the candidate tile must be a 2-D float32 device tensor, got {tuple(cand.shape)} {cand.dtype}")
+    _check_cand_tile("rank_merge", cand)
     R, B = cand.shape
     _check_rank_state("rank_merge", counts, key_vals, key_ids, R)
     cand, ld = _tile_view(cand)
@@ -1197,9 +1235,7 @@ def rank_keys(x: torch.Tensor, y: torch.Tensor, targets: torch.Tensor, chunk_row
     pos = torch.searchsorted(uniq, targets.clamp(min=0)).to(xd.device)  # the column of yu that holds targets[r, t]
     used = used.to(xd.device)
     yu = _f32c(y[uniq.to(y.device)], xd.device)
-    U = yu.shape[0]
-    step = min(chunk_rows or topk_chunk_rows(R, U), U)
-    for _, _, c0, nc, out in _cosine_tiles(xd, yu, R, step):
+    for _, _, c0, nc, out in _row_tiles(xd, yu, chunk_rows)[1]:
         here = used & (pos >= c0) & (pos < c0 + nc)
         vals = torch.where(here, out.gather(1, (pos - c0).clamp(0, nc - 1)), vals)
     return vals
@@ -1211,27 +1247,17 @@ def rank_probe(x: torch.Tensor, y: torch.Tensor, key_vals: torch.Tensor, key_ids
     has the id ``id_base + j``) whose cosine orders before the key ``(key_vals, key_ids) (R, T)``.  Returns (and continues, as
     ``state``) the ``(R, T)`` int64 counts; slots with a negative key id stay as they are.  ``softmax=(state, scale)``: K25 folds the
     same tiles into that ``(R, 4)`` softmax state, as ``softmax_probe`` does."""
-    _check_probe_args("rank_probe", x, y, chunk_rows=chunk_rows)
-    xd = _f32c(x)
-    yd = _f32c(y, xd.device)
-    R, n = xd.shape[0], yd.shape[0]
-    counts = state if state is not None else torch.zeros(key_ids.shape, dtype=torch.int64, device=xd.device)
-    _check_rank_state("rank_probe", counts, key_vals, key_ids, R)
-    sm, scale = softmax if softmax is not None else (None, None)
-    if sm is not None:
-        scale = check_logit_scale(scale)
-        _check_softmax_state("rank_probe", sm, R)
-    if R == 0 or n == 0:
-        return counts
-    step = min(chunk_rows or topk_chunk_rows(R, n), n)
-    tiles = _cosine_tiles(xd, yd, R, step)
-    merge_bytes = int(lib().sl_softmax_merge_ws_bytes(R, step)) if sm is not None else 0
-    merge_ws = torch.empty(merge_bytes, dtype=torch.uint8, device=xd.device) if merge_bytes else None
-    for _, _, c0, _, out in tiles:
-        rank_merge(counts, out, key_vals, key_ids, id_base + c0)
-        if sm is not None:
-            softmax_merge(sm, out, scale, merge_ws)
-    return counts
+    def setup(R, device):
+        counts = state if state is not None else torch.zeros(key_ids.shape, dtype=torch.int64, device=device)
+        _check_rank_state("rank_probe", counts, key_vals, key_ids, R)
+        folds = [_Fold(lambda R, step: 0, lambda out, c0, ws: rank_merge(counts, out, key_vals, key_ids, id_base + c0))]  # no workspace
+        if softmax is not None and softmax[0] is not None:
+            sm, scale = softmax[0], check_logit_scale(softmax[1])
+            _check_softmax_state("rank_probe", sm, R)
+            folds.append(_softmax_fold(sm, scale))
+        return counts, folds
+
+    return _row_probe("rank_probe", x, y, chunk_rows, setup)
 
 # ------------------------------------------------------------------------------------------------
 # K20: mutual best matches (row and column maxima of every cosine tile in one read)
@@ -1252,8 +1278,7 @@ def mutualmax_merge(row_state: torch.Tensor, col_state: torch.Tensor, cand: torc
     every row — and ``col_state (B,)`` — the best row of every column — in one read of the tile.  States are int64 tensors of
     packed entries (``torch.zeros`` is the empty state; decode with ``mutualmax_finish``); row ``r`` has the id
     ``row_id_base + r``, column ``j`` the id ``col_id_base + j``, all within ``[0, MUTUALMAX_MAX_ID]``."""
-    if cand.ndim != 2 or cand.dtype != torch.float32 or not cand.is_cuda:
-        raise ValueError(f"mutualmax_merge: the candidate tile must be a 2-D float32 device tensor, got {tuple(cand.shape)} {cand.dtype}")
+    _check_cand_tile("mutualmax_merge", cand)
     R, B = cand.shape
     _check_mutualmax_state("mutualmax_merge", row_state, R)
     _check_mutualmax_state("mutualmax_merge", col_state, B)
@@ -1307,8 +1332,7 @@ def segmax_merge(state: torch.Tensor, cand: torch.Tensor, row_seg: torch.Tensor,
     ignored).  ``state`` is an int64 device tensor of K20's packed entries with unit column stride and any row stride — a column
     slice of a ``(G, C)`` state — and ``torch.zeros`` is the empty state; ``row_seg`` is ``(R,)`` int32 on the device; row ``r``
     has the id ``row_id_base + r`` within ``[0, MUTUALMAX_MAX_ID]``."""
-    if cand.ndim != 2 or cand.dtype != torch.float32 or not cand.is_cuda:
-        raise ValueError(f"segmax_merge: the candidate tile must be a 2-D float32 device tensor, got {tuple(cand.shape)} {cand.dtype}")
+    _check_cand_tile("segmax_merge", cand)
     R, B = cand.shape
     if state.ndim != 2 or state.dtype != torch.int64 or state.device != cand.device or state.shape[1] != B:
         raise ValueError(f"segmax_merge: the state must be a (G, {B}) int64 tensor on {cand.device}, got {tuple(state.shape)} "
@@ -1426,12 +1450,6 @@ def _check_status(what: str, status: torch.Tensor, device):
         raise ValueError(f"{what}: the status word is one int32 on {device}, got {tuple(status.shape)} {status.dtype} on {status.device}")
 
 
-def _check_tile(what: str, cand: torch.Tensor, device):
-    if cand.ndim != 2 or cand.dtype != torch.float32 or cand.device != device:
-        raise ValueError(f"{what}: the candidate tile must be a 2-D float32 tensor on {device}, got {tuple(cand.shape)} {cand.dtype} "
-                         f"on {cand.device}")
-
-
 def unionfind_new(n: int, device) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
     """The empty state ``(parent (n,), degree (n,), status (1,))``, all int32: ``parent[i] = i``, zeros."""
     parent = torch.empty(n, dtype=torch.int32, device=device)
@@ -1448,7 +1466,7 @@ def threshold_union_merge(parent: torch.Tensor, degree: torch.Tensor, status: to
     components: every element with ``row_id_base + r < col_id_base + c`` and a value ``>= threshold`` is an edge."""
     n = _check_states("threshold_union_merge", parent, degree)
     _check_status("threshold_union_merge", status, parent.device)
-    _check_tile("threshold_union_merge", cand, parent.device)
+    _check_cand_tile("threshold_union_merge", cand, parent.device)
     R, B = cand.shape
     cand, ld = _tile_view(cand)
     with _on(cand.device):
@@ -1469,7 +1487,7 @@ def group_min_merge(state: torch.Tensor, labels: torch.Tensor, cand: torch.Tenso
     """Fold the tile into ``state (n,)`` int32 (``torch.full(-1)`` is the empty state): entry ``label`` takes the smallest order
     key among the upper-triangle elements whose row and column both carry ``label`` in ``labels (n,)`` int32."""
     n = _check_states("group_min_merge", state, labels)
-    _check_tile("group_min_merge", cand, state.device)
+    _check_cand_tile("group_min_merge", cand, state.device)
     R, B = cand.shape
     cand, ld = _tile_view(cand)
     with _on(cand.device):

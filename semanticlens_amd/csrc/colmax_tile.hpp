@@ -17,7 +17,6 @@
 
 namespace sl {
 
-typedef float f4 __attribute__((ext_vector_type(4)));
 typedef unsigned long long u64;
 
 namespace coltile {

@@ -15,6 +15,8 @@ namespace sl {
 
 constexpr int kWave = 64;  // gfx950 wavefront
 
+typedef float f4 __attribute__((ext_vector_type(4)));  // one 16-byte load (colmax_tile.hpp, rowseg_tile.hpp)
+
 // ---- error plumbing -------------------------------------------------------------------
 void set_error(const char* fmt, ...);
 int hip_fail(hipError_t e, const char* what);

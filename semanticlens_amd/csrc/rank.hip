@@ -17,14 +17,13 @@
 // Few rows of very many columns: the columns are split over S waves per row (the rule K17 uses), and the S partial counts go into
 // the row's counts with 64-bit integer atomic adds.  Integer addition is associative and commutative: the counts after a sequence
 // of merges do not depend on the cut into tiles, their order or the scheduling.  No workspace, no second launch.
-#include "colmax_tile.hpp"  // f4
 #include "rank_order.hpp"
+#include "rowseg_tile.hpp"
 
 namespace sl {
 namespace {
 
-constexpr int kChunk = 16 * kWave;     // columns a wave holds in registers at a time
-constexpr int64_t kMinSegment = 1024;  // columns per wave when a row is split
+using rowseg::kChunk;
 constexpr int kMaxTargets = SL_RANK_MAX_TARGETS;
 
 // One wave per (row, split): columns [s*seg, (s+1)*seg) of the row.  TP: the slots the kernel is built for (1, 4 or 16: more
@@ -36,9 +35,7 @@ __global__ __launch_bounds__(64) void rank_tile_kernel(int64_t* __restrict__ cou
                                                          const int64_t* __restrict__ key_ids, int S, int64_t seg) {
   const int lane = threadIdx.x;
   for (int64_t w = blockIdx.x; w < R * S; w += gridDim.x) {
-    const int64_t row = w / S;
-    const int s = (int)(w % S);
-    const int64_t lo = s * seg, hi = lo + seg < B ? lo + seg : B;
+    const auto [row, s, lo, hi] = rowseg::item(w, S, seg, B);
     const float* rowp = cand + row * ld;
     uint32_t key[TP];
     int64_t kid[TP];
@@ -49,9 +46,7 @@ __global__ __launch_bounds__(64) void rank_tile_kernel(int64_t* __restrict__ cou
       key[t] = t < T ? f32_order_key(key_vals[row * T + t]) : 0u;
       total[t] = 0;
     }
-    // 16-byte pieces at 16-byte aligned addresses; a piece that straddles lo or hi is read element by element
-    const int64_t a0 = lo - (int64_t)(((uintptr_t)(rowp + lo) >> 2) & 3);
-    for (int64_t base = a0; base < hi; base += kChunk) {
+    for (int64_t base = rowseg::chunk_start((uintptr_t)(rowp + lo), lo); base < hi; base += kChunk) {
       uint32_t ck[4][4];
       if (base >= lo && base + kChunk <= hi) {  // wave-uniform: the whole chunk lies inside, four loads in flight at once
         f4 x[4];
@@ -61,7 +56,7 @@ __global__ __launch_bounds__(64) void rank_tile_kernel(int64_t* __restrict__ cou
         for (int u = 0; u < 4; ++u)
 #pragma unroll
           for (int j = 0; j < 4; ++j) ck[u][j] = f32_order_key(x[u][j]);
-      } else {  // a segment's first or last chunk
+      } else {  // a segment's first or last chunk: rowseg::load_chunk's guards, spelled out (rowseg_tile.hpp says why)
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
           const int64_t c = base + (int64_t)(u * kWave + lane) * 4;
@@ -113,25 +108,10 @@ __global__ __launch_bounds__(64) void rank_tile_kernel(int64_t* __restrict__ cou
   }
 }
 
-// waves per row: enough to give every CU eight waves, each with at least kMinSegment columns (K17's rule)
-int64_t splits(int64_t R, int64_t B) {
-  if (R <= 0) return 1;
-  const int64_t want = ((int64_t)num_cus() * 8 + R - 1) / R;
-  const int64_t can = B / kMinSegment;
-  const int64_t s = want < can ? want : can;
-  return s < 2 ? 1 : s;
-}
-
-// one-wave workgroups: a few items per wave slot
-int64_t wave_grid(int64_t items) {
-  const int64_t cap = (int64_t)num_cus() * 32 * 4;
-  return items < cap ? items : cap;
-}
-
 template <int TP>
 void launch(ProfScope& prof, hipStream_t st, int64_t items, int64_t* counts, int64_t R, int T, const float* cand, int64_t ld, int64_t B,
             int64_t id_base, const float* key_vals, const int64_t* key_ids, int S, int64_t seg) {
-  SL_LAUNCH(prof, rank_tile_kernel<TP>, dim3((unsigned)wave_grid(items)), dim3(64), 0, st, counts, R, T, cand, ld, B, id_base, key_vals,
+  SL_LAUNCH(prof, rank_tile_kernel<TP>, dim3((unsigned)rowseg::wave_grid(items, num_cus(), 32)), dim3(64), 0, st, counts, R, T, cand, ld, B, id_base, key_vals,
             key_ids, S, seg);
 }
 
@@ -140,24 +120,22 @@ void launch(ProfScope& prof, hipStream_t st, int64_t items, int64_t* counts, int
 
 using namespace sl;
 
-SL_API int64_t sl_rank_merge_splits(int64_t R, int64_t B) { return R <= 0 || B < 1 ? 1 : splits(R, B); }
+SL_API int64_t sl_rank_merge_splits(int64_t R, int64_t B) { return R <= 0 || B < 1 ? 1 : rowseg::splits(R, B, num_cus()); }
 
 SL_API int sl_rank_merge(int64_t* d_counts, int64_t R, int64_t T, const float* d_cand, int64_t ld, int64_t B, int64_t id_base,
                          const float* d_key_vals, const int64_t* d_key_ids, void* stream) {
   SL_REQUIRE(R >= 0, "sl_rank_merge: negative row count");
   SL_REQUIRE(T >= 1 && T <= kMaxTargets, "sl_rank_merge: T = %lld not in [1, %d]", (long long)T, kMaxTargets);
-  SL_REQUIRE(B >= 1, "sl_rank_merge: B = %lld, a tile has at least one column", (long long)B);
-  SL_REQUIRE(ld >= B, "sl_rank_merge: row stride %lld below B = %lld", (long long)ld, (long long)B);
+  if (int rc = rowseg::check_tile_shape("sl_rank_merge", B, ld)) return rc;
   SL_REQUIRE(id_base >= 0 && id_base <= (1ll << 62), "sl_rank_merge: id_base %lld outside [0, 2^62]", (long long)id_base);
   if (R == 0) return 0;
   SL_REQUIRE(d_counts && d_cand && d_key_vals && d_key_ids, "sl_rank_merge: null counts, candidate tile or keys");
   SL_REQUIRE(((uintptr_t)d_counts & 7) == 0 && ((uintptr_t)d_key_ids & 7) == 0, "sl_rank_merge: counts or key ids are not 8-byte aligned");
   SL_REQUIRE(((uintptr_t)d_cand & 3) == 0 && ((uintptr_t)d_key_vals & 3) == 0, "sl_rank_merge: candidate tile or key values are not 4-byte aligned");
-  const int64_t S = splits(R, B);
-  SL_REQUIRE(R <= 0x7FFFFFFFll / S, "sl_rank_merge: %lld rows in %lld segments are more than 2^31 - 1 items; cut the tile", (long long)R,
-             (long long)S);
+  const int64_t S = rowseg::splits(R, B, num_cus());
+  if (int rc = rowseg::check_items("sl_rank_merge", R, S)) return rc;
   hipStream_t st = (hipStream_t)stream;
-  const int64_t seg = S == 1 ? B : (B + S - 1) / S;
+  const int64_t seg = rowseg::segment(B, S);
   ProfScope prof(SL_PROF_TOPK, st, (double)R * (double)B * 4);
   const int t = (int)T;
   if (t == 1)

@@ -23,7 +23,7 @@
 // Few rows of very many columns: the columns are split over S waves per row (the rule K17 uses), each of which writes its
 // segment's state to the workspace, and a second launch folds a row's S states into the row's state, one wave per row, in a
 // fixed order.  No floating-point atomics anywhere: the same calls give the same bits.
-#include "colmax_tile.hpp"  // f4
+#include "rowseg_tile.hpp"
 #include "softmax_state.hpp"
 
 namespace sl {
@@ -31,9 +31,7 @@ namespace {
 
 using softmax::State;
 
-constexpr int kChunk = 16 * kWave;     // columns a wave holds in registers at a time
-constexpr int64_t kMinSegment = 1024;  // columns per wave when a row is split
-constexpr int kMaxK = 1024;            // K17's
+constexpr int kMaxK = 1024;  // K17's
 constexpr double kLog2e = 1.44269504088896340736;
 constexpr double kLn2 = 0.693147180559945309417;
 
@@ -51,26 +49,13 @@ __global__ __launch_bounds__(64) void softmax_tile_kernel(State* __restrict__ st
                                                             State* __restrict__ ws) {
   const int lane = threadIdx.x;
   for (int64_t w = blockIdx.x; w < R * S; w += gridDim.x) {
-    const int64_t row = w / S;
-    const int s = (int)(w % S);
-    const int64_t lo = s * seg, hi = lo + seg < B ? lo + seg : B;
+    const auto [row, s, lo, hi] = rowseg::item(w, S, seg, B);
     const float* rowp = cand + row * ld;
     float M = -INFINITY;                // wave-uniform: the largest finite candidate so far
     double A = 0.0, Bn = 0.0, Sp = 0.0;  // the lane's sums against M (Bn in nats); Sp: parked non-finite sums
-    // 16-byte pieces at 16-byte aligned addresses; a piece that straddles lo or hi is read element by element
-    const int64_t a0 = lo - (int64_t)(((uintptr_t)(rowp + lo) >> 2) & 3);
-    for (int64_t base = a0; base < hi; base += kChunk) {
+    for (int64_t base = rowseg::chunk_start((uintptr_t)(rowp + lo), lo); base < hi; base += rowseg::kChunk) {
       f4 x[4];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const int64_t c = base + (int64_t)(u * kWave + lane) * 4;
-        if (c >= lo && c + 4 <= hi) {
-          x[u] = *reinterpret_cast<const f4*>(rowp + c);
-        } else {
-#pragma unroll
-          for (int j = 0; j < 4; ++j) x[u][j] = (c + j >= lo && c + j < hi) ? rowp[c + j] : -INFINITY;  // -inf adds nothing
-        }
-      }
+      rowseg::load_chunk(rowp, base, lo, hi, lane, -INFINITY, x);  // -inf adds nothing
       float bm = -INFINITY;  // fmaxf drops a NaN: those reach the sums below
 #pragma unroll
       for (int u = 0; u < 4; ++u)
@@ -160,20 +145,7 @@ __global__ __launch_bounds__(256) void softmax_finish_kernel(const State* __rest
   }
 }
 
-// waves per row: enough to give every CU eight waves, each with at least kMinSegment columns (K17's rule)
-int64_t splits(int64_t R, int64_t B) {
-  if (R <= 0) return 1;
-  const int64_t want = ((int64_t)num_cus() * 8 + R - 1) / R;
-  const int64_t can = B / kMinSegment;
-  const int64_t s = want < can ? want : can;
-  return s < 2 ? 1 : s;
-}
-
-// one-wave workgroups: a few items per wave slot
-int64_t wave_grid(int64_t items) {
-  const int64_t cap = (int64_t)num_cus() * 32 * 4;
-  return items < cap ? items : cap;
-}
+int64_t wave_grid(int64_t items) { return rowseg::wave_grid(items, num_cus(), 32); }
 
 int check_state(const char* fn, int64_t R, const void* state) {
   SL_REQUIRE(R >= 0, "%s: negative row count", fn);
@@ -203,22 +175,19 @@ SL_API int sl_softmax_init(double* d_state, int64_t R, void* stream) {
 
 SL_API size_t sl_softmax_merge_ws_bytes(int64_t R, int64_t B) {
   if (R <= 0 || B < 1) return 0;
-  const int64_t S = splits(R, B);
+  const int64_t S = rowseg::splits(R, B, num_cus());
   return S > 1 ? (size_t)R * (size_t)S * sizeof(State) + 256 : 0;
 }
 
 SL_API int sl_softmax_merge(double* d_state, int64_t R, const float* d_cand, int64_t ld, int64_t B, double scale, void* d_ws,
                             size_t ws_bytes, void* stream) {
   if (int rc = check_state("sl_softmax_merge", R, d_state)) return rc;
-  SL_REQUIRE(B >= 1, "sl_softmax_merge: B = %lld, a tile has at least one column", (long long)B);
-  SL_REQUIRE(ld >= B, "sl_softmax_merge: row stride %lld below B = %lld", (long long)ld, (long long)B);
+  if (int rc = rowseg::check_tile_shape("sl_softmax_merge", B, ld)) return rc;
   if (int rc = check_scale("sl_softmax_merge", scale)) return rc;
   if (R == 0) return 0;
-  SL_REQUIRE(d_cand, "sl_softmax_merge: null candidate tile");
-  SL_REQUIRE(((uintptr_t)d_cand & 3) == 0, "sl_softmax_merge: candidate tile is not 4-byte aligned");
-  const int64_t S = splits(R, B);
-  SL_REQUIRE(R <= 0x7FFFFFFFll / S, "sl_softmax_merge: %lld rows in %lld segments are more than 2^31 - 1 items; cut the tile",
-             (long long)R, (long long)S);
+  if (int rc = rowseg::check_tile_ptr("sl_softmax_merge", d_cand)) return rc;
+  const int64_t S = rowseg::splits(R, B, num_cus());
+  if (int rc = rowseg::check_items("sl_softmax_merge", R, S)) return rc;
   hipStream_t st = (hipStream_t)stream;
   const float s2 = (float)(scale * kLog2e);  // one rounding
   SL_REQUIRE(s2 >= 1.17549435e-38f && s2 < INFINITY, "sl_softmax_merge: logit scale %g leaves fp32's normal range", scale);
@@ -230,8 +199,8 @@ SL_API int sl_softmax_merge(double* d_state, int64_t R, const float* d_cand, int
     return 0;
   }
   SL_REQUIRE(d_ws && ws_bytes >= sl_softmax_merge_ws_bytes(R, B), "sl_softmax_merge: workspace too small");
-  State* ws = (State*)(((uintptr_t)d_ws + 255) & ~(uintptr_t)255);
-  const int64_t seg = (B + S - 1) / S;
+  State* ws = (State*)rowseg::align_ws(d_ws);
+  const int64_t seg = rowseg::segment(B, S);
   SL_LAUNCH(prof, softmax_tile_kernel, dim3((unsigned)wave_grid(R * S)), dim3(64), 0, st, (State*)d_state, R, d_cand, ld, B, scale, s2,
             (int)S, seg, ws);
   ProfScope fold(SL_PROF_SOFTMAX, st, (double)R * (double)S * sizeof(State));

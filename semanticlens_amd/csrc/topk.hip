@@ -18,15 +18,15 @@
 // Few rows (search: a handful of queries against tens of thousands of components): the columns are split over S waves per
 // row, each of which selects its segment's top k into a workspace (filtered by the state's k-th entry: what that rejects
 // cannot reach the result), and a second launch folds the S lists into the state with the explicit-id kernel.
-#include "colmax_tile.hpp"  // f4; f32_order_key through packed_best.hpp
+#include "packed_best.hpp"  // f32_order_key
+#include "rowseg_tile.hpp"
 
 namespace sl {
 namespace {
 
 constexpr int kMaxK = 1024;
 constexpr int64_t kMaxId = (int64_t)1 << 62;
-constexpr int kMinBuf = 128;          // room behind the state: at least two appends of 64
-constexpr int64_t kMinSegment = 1024;  // columns per wave when a row is split
+constexpr int kMinBuf = 128;  // room behind the state: at least two appends of 64
 
 // f32_order_key (packed_best.hpp) of a slot; the empty slot's key is 0, below every real value's
 __device__ inline uint32_t entry_key(float v, int64_t id) { return id < 0 ? 0u : f32_order_key(v); }
@@ -129,9 +129,7 @@ __global__ __launch_bounds__(64) void topk_tile_kernel(float* __restrict__ vals,
   st.id = reinterpret_cast<int64_t*>(smem);
   st.v = reinterpret_cast<float*>(smem + (size_t)st.n * 8);
   for (int64_t w = blockIdx.x; w < R * S; w += gridDim.x) {
-    const int64_t row = w / S;
-    const int s = (int)(w % S);
-    const int64_t lo = s * seg, hi = lo + seg < B ? lo + seg : B;
+    const auto [row, s, lo, hi] = rowseg::item(w, S, seg, B);
     float* gv = vals + row * k;
     int64_t* gid = ids + row * k;
     __syncthreads();  // the previous item's stores have read the LDS
@@ -143,20 +141,9 @@ __global__ __launch_bounds__(64) void topk_tile_kernel(float* __restrict__ vals,
     }
     bool touched = false;
     const float* rowp = cand + row * ld;
-    // 16-byte pieces at 16-byte aligned addresses; a piece that straddles lo or hi is read element by element
-    const int64_t a0 = lo - (int64_t)(((uintptr_t)(rowp + lo) >> 2) & 3);
-    for (int64_t base = a0; base < hi; base += 4 * 4 * kWave) {
+    for (int64_t base = rowseg::chunk_start((uintptr_t)(rowp + lo), lo); base < hi; base += rowseg::kChunk) {
       f4 x[4];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const int64_t c = base + (int64_t)(u * kWave + lane) * 4;
-        if (c >= lo && c + 4 <= hi) {
-          x[u] = *reinterpret_cast<const f4*>(rowp + c);
-        } else {
-#pragma unroll
-          for (int j = 0; j < 4; ++j) x[u][j] = (c + j >= lo && c + j < hi) ? rowp[c + j] : 0.f;
-        }
-      }
+      rowseg::load_chunk(rowp, base, lo, hi, lane, 0.f, x);
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
         // the common case: no key in these 256 columns reaches the k-th entry's (columns outside [lo,hi) read as 0.0 and are
@@ -227,21 +214,11 @@ __global__ __launch_bounds__(256) void topk_init_kernel(float* __restrict__ vals
 
 size_t lds_bytes(int64_t k) { return (size_t)pow2_entries((int)k) * 12; }
 
-// waves per row: enough to give every CU eight waves, each with at least kMinSegment columns
-int64_t splits(int64_t R, int64_t B) {
-  if (R <= 0) return 1;
-  const int64_t want = ((int64_t)num_cus() * 8 + R - 1) / R;
-  const int64_t can = B / kMinSegment;
-  const int64_t s = want < can ? want : can;
-  return s < 2 ? 1 : s;
-}
-
 int64_t wave_grid(int64_t items, int64_t k) {
   int64_t per_cu = (int64_t)(160 * 1024 / lds_bytes(k));  // resident one-wave workgroups per CU
   if (per_cu > 32) per_cu = 32;
   if (per_cu < 1) per_cu = 1;
-  const int64_t cap = (int64_t)num_cus() * per_cu * 4;  // a few items per wave slot evens out rows with many insertions
-  return items < cap ? items : cap;
+  return rowseg::wave_grid(items, num_cus(), per_cu);
 }
 
 int check_state(const char* fn, int64_t R, int64_t k) {
@@ -267,21 +244,19 @@ SL_API int sl_topk_init(float* d_vals, int64_t* d_ids, int64_t R, int64_t k, voi
 
 SL_API size_t sl_topk_merge_ws_bytes(int64_t R, int64_t k, int64_t B) {
   if (R <= 0 || k < 1 || k > kMaxK || B < 1) return 0;
-  const int64_t S = splits(R, B);
+  const int64_t S = rowseg::splits(R, B, num_cus());
   return S > 1 ? (size_t)R * (size_t)S * (size_t)k * 12 + 256 : 0;
 }
 
 SL_API int sl_topk_merge(float* d_vals, int64_t* d_ids, int64_t R, int64_t k, const float* d_cand, int64_t ld, int64_t B,
                          int64_t id_base, void* d_ws, size_t ws_bytes, void* stream) {
   if (int rc = check_state("sl_topk_merge", R, k)) return rc;
-  SL_REQUIRE(B >= 1, "sl_topk_merge: B = %lld, a tile has at least one column", (long long)B);
-  SL_REQUIRE(ld >= B, "sl_topk_merge: row stride %lld below B = %lld", (long long)ld, (long long)B);
+  if (int rc = rowseg::check_tile_shape("sl_topk_merge", B, ld)) return rc;
   SL_REQUIRE(id_base >= 0 && id_base <= kMaxId - B, "sl_topk_merge: ids from id_base = %lld leave [0, 2^62]", (long long)id_base);
   if (R == 0) return 0;
   SL_REQUIRE(d_vals && d_ids, "sl_topk_merge: null state");
-  SL_REQUIRE(d_cand, "sl_topk_merge: null candidate tile");
-  SL_REQUIRE(((uintptr_t)d_cand & 3) == 0, "sl_topk_merge: candidate tile is not 4-byte aligned");
-  const int64_t S = splits(R, B);
+  if (int rc = rowseg::check_tile_ptr("sl_topk_merge", d_cand)) return rc;
+  const int64_t S = rowseg::splits(R, B, num_cus());
   hipStream_t st = (hipStream_t)stream;
   ProfScope prof(SL_PROF_TOPK, st, (double)R * (double)B * 4);
   if (S == 1) {
@@ -291,9 +266,9 @@ SL_API int sl_topk_merge(float* d_vals, int64_t* d_ids, int64_t R, int64_t k, co
     return 0;
   }
   SL_REQUIRE(d_ws && ws_bytes >= sl_topk_merge_ws_bytes(R, k, B), "sl_topk_merge: workspace too small");
-  int64_t* wid = (int64_t*)(((uintptr_t)d_ws + 255) & ~(uintptr_t)255);
+  int64_t* wid = (int64_t*)rowseg::align_ws(d_ws);
   float* wv = (float*)(wid + R * S * k);
-  const int64_t seg = (B + S - 1) / S;
+  const int64_t seg = rowseg::segment(B, S);
   SL_LAUNCH(prof, topk_tile_kernel, dim3((unsigned)wave_grid(R * S, k)), dim3(64), lds_bytes(k), st, d_vals, d_ids, R, (int)k,
             d_cand, ld, B, id_base, (int)S, seg, wv, wid);
   ProfScope fold(SL_PROF_TOPK, st, (double)R * (double)S * (double)k * 12);

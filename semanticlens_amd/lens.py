@@ -329,10 +329,10 @@ def probe_softmax(query_embeds: torch.Tensor, aggregated_concept_db, k: int, log
     folds each tile K17 reads into a four-double state per component."""
     k = N.check_topk_k(k)
     scale = N.check_logit_scale(logit_scale)
-    if chunk_rows is not None and chunk_rows < 1:
-        raise ValueError(f"chunk_rows = {chunk_rows} must be at least 1")
     names, layers, is_dict = _db_layers(aggregated_concept_db)
     _check_width(query_embeds, layers)
+    for layer in layers:  # the probe's own check, made here too because _probe_layers moves a layer to the device before it probes
+        N._check_probe_args("probe_softmax", layer, query_embeds, chunk_rows=chunk_rows)
 
     def probe(ld, q):
         vals, ids, sm = N.softmax_probe(ld, q, k, scale, chunk_rows)

@@ -899,6 +899,77 @@ def test_packed_best_header_on_the_host(tmp_path):
     assert "failures=0" in res.stdout
 
 
+def test_rowseg_tile_header_on_the_host(tmp_path):
+    """The pure part of csrc/rowseg_tile.hpp compiled for the host: the waves per row of K17 / K25 / K26 on a table recorded from
+    the kernels' former copies of the rule, the segments' cover of a row, and the aligned start of a wave's walk
+    (tests/native/rowseg_tile_check.cpp)."""
+    exe = tmp_path / "rowseg_tile_check"
+    subprocess.run(["g++", "-O2", "-std=c++17", "-Wall", "-Wextra", "-o", str(exe),
+                    str(ROOT / "tests" / "native" / "rowseg_tile_check.cpp")], check=True)
+    res = subprocess.run([str(exe)], capture_output=True, text=True)
+    assert res.returncode == 0, res.stdout + res.stderr
+    assert "failures=0" in res.stdout
+
+
+@pytest.mark.parametrize("R,n,chunk_rows", [(3, 10, 4), (3, 10, None), (1, 1, 1), (0, 5, None), (5, 0, None)])
+def test_row_probe_driver_walks_the_tiles_once_for_all_folds(monkeypatch, R, n, chunk_rows):
+    """`_native._row_probe`, the walk under `topk_probe`, `softmax_probe` and `rank_probe`, with a fake cosine GEMM and recording
+    folds, no device: tiles at c0 = 0, step, 2 step, ... with the last one narrower; every fold gets the same tile, in list order;
+    one workspace, sized once as the largest fold's at `step`; nothing runs for an empty operand."""
+    log, tiles_made = [], []
+
+    def fake_cosine_tiles(xd, yd, rows, cols, walk=None):
+        log.append(("tiles", rows, cols))  # the call allocates the tile buffer: before the workspace and the first merge
+
+        def tiles():
+            for c0 in range(0, yd.shape[0], cols):
+                nc = min(cols, yd.shape[0] - c0)
+                tiles_made.append(torch.full((rows, nc), float(c0)))
+                yield 0, rows, c0, nc, tiles_made[-1]
+
+        return tiles()
+
+    monkeypatch.setattr(N, "_cosine_tiles", fake_cosine_tiles)
+    monkeypatch.setattr(N, "_f32c", lambda t, device=None: t.to(torch.float32).contiguous())
+
+    def fold(name, nbytes):
+        return N._Fold(lambda rows, step: log.append(("ws_bytes", name, rows, step)) or nbytes,
+                       lambda out, c0, ws: log.append(("merge", name, c0, out, ws)))
+
+    def setup(rows, device):
+        log.append(("setup", rows, device))
+        return "the state", [fold("a", 48), fold("b", 112), fold("c", 0)]
+
+    x, y = torch.zeros(R, 8), torch.zeros(n, 8)
+    assert N._row_probe("probe", x, y, chunk_rows, setup) == "the state"
+    assert log[0] == ("setup", R, x.device)
+    if R == 0 or n == 0:
+        assert log[1:] == []
+        return
+    step = min(chunk_rows or N.topk_chunk_rows(R, n), n)
+    assert log[1] == ("tiles", R, step)
+    assert log[2:5] == [("ws_bytes", f, R, step) for f in "abc"]  # sized once, before the first tile is asked for
+    merges = log[5:]
+    starts = list(range(0, n, step))
+    assert [(kind, f, c0) for kind, f, c0, _, _ in merges] == [("merge", f, c0) for c0 in starts for f in "abc"]
+    assert len(tiles_made) == len(starts) and tiles_made[-1].shape == (R, n - starts[-1])
+    for i, (_, _, _, out, ws) in enumerate(merges):
+        assert out is tiles_made[i // 3]
+        assert ws is merges[0][4] and ws.dtype == torch.uint8 and ws.numel() == 112
+
+
+def test_row_probe_driver_checks_its_arguments_first():
+    def setup(rows, device):
+        raise AssertionError("the state is set up only after the checks")
+
+    with pytest.raises(ValueError, match="chunk_rows = 0 must be at least 1"):
+        N._row_probe("probe", torch.zeros(3, 8), torch.zeros(10, 8), 0, setup)
+    with pytest.raises(ValueError, match="probe expects 2-D"):
+        N._row_probe("probe", torch.zeros(8), torch.zeros(10, 8), None, setup)
+    with pytest.raises(ValueError, match="widths differ"):
+        N._row_probe("probe", torch.zeros(3, 8), torch.zeros(10, 4), None, setup)
+
+
 # (m, n, chunk_rows, chunk_cols) -> the (rows, cols) of the tile, from the probes' expressions before `tile_plan` existed:
 # cols = min(chunk_cols or min(n, TOPK_TILE_BYTES // 4), n), rows = min(chunk_rows or topk_chunk_rows(cols, m), m)
 TILE_PLANS = {
