@@ -230,6 +230,8 @@ int sl_gather_rows_shard(const float* d_emb_local, int64_t n_local, int64_t D, c
  * normalize(y) (xc == yr; out (xr,yc)), 2 normalize(x) @ normalize(y)^T (xc == yc; out
  * (xr,yr)); SL_E_INVALID for incompatible shapes (the reference raises ValueError).
  * d_ws: scratch of sl_similarity_ws_bytes(...) bytes.
+ * Empty operands follow torch: an output without elements is left alone, and with xc == 0 (every branch contracts over xc)
+ * the output is set to zeros; no kernel runs, and d_x / d_y may be NULL in both cases.
  * Arithmetic of the plain branch: split-bf16 x3 on the bf16 matrix cores (|error| ~1e-6 on cosines) when
  * K >= 64, else fp32-input MFMA; SL_GEMM_MODE=f32 in the environment forces the latter. */
 int sl_similarity(const float* d_x, int64_t xr, int64_t xc, const float* d_y, int64_t yr, int64_t yc, float* d_out,

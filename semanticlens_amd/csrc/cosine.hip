@@ -471,7 +471,17 @@ SL_API int sl_similarity(const float* d_x, int64_t xr, int64_t xc, const float* 
     set_error("x and y must have the same shape");  // the reference's ValueError text (scores.py:126)
     return SL_E_INVALID;
   }
-  if (xr * xc == 0 && same) return 0;
+  // Empty operands, as torch treats them: every branch contracts over xc, so an output without elements is left alone and a
+  // contraction over nothing is all zeros (F.cosine_similarity and F.normalize + matmul both give 0).  No kernel runs, and
+  // d_x / d_y may be NULL, which is how the Python side passes an empty tensor.
+  const int branch = same ? 0 : (xc == yr ? 1 : 2);
+  const int64_t n_out = same ? xr : xr * (branch == 1 ? yc : yr);
+  if (n_out == 0) return branch;
+  if (xc == 0) {
+    SL_REQUIRE(d_out, "sl_similarity: null pointer");
+    SL_CHECK_HIP(hipMemsetAsync(d_out, 0, (size_t)n_out * 4, st));
+    return branch;
+  }
   SL_REQUIRE(d_x && d_y && d_out, "sl_similarity: null pointer");
   if (same) {
     int64_t blocks = (xr + 3) / 4;

@@ -1174,7 +1174,10 @@ def test_every_arm_of_the_gemm_launch_switch_gives_the_register_staged_kernels_b
     128 x 128 ring, register-staged (7 k-tiles), 160 x 256, 8-phase, a column cut (8-phase + strip), and the fp32 mode's 8-phase /
     vectorised / scalar kernels — by the dispatcher's own rule (tile option 0) against the 128 x 128 register-staged kernel forced:
     same bits.  Which kernel a shape gets is tests/native/gemm_choice_check.cpp's subject, not this test's.  (161, 257, 20) has
-    K < 64, where `similarity` takes the fp32 GEMM in either mode.)  In-process: options are read per dispatch."""
+    K < 64, where `similarity` takes the fp32 GEMM in either mode.)  In-process: options are read per dispatch.
+    The f32 cases (130, 257, 72) and (129, 128, 73) compare a kernel with itself: `choose_f32` takes the 8-phase kernel only at
+    K % 32 == 0, so f32_tile = 0 and = 128 both give `Vec128` (72) and `Scalar128` (73).  They show that the forced option does no
+    harm there; what holds those two kernels to a reference is tests/test_gpu_cosine_paths.py."""
     g3_shapes = [(130, 257, 256), (1, 5, 4096), (2304, 1024, 256), (2304, 1024, 200), (161, 257, 20), (12800, 768, 256),
                  (8192, 2048, 256), (10000, 9216, 1152), (16384, 1152, 256), (300, 301, 104)]
     f32_shapes = [(8192, 2048, 256), (130, 257, 72), (129, 128, 73)]
