@@ -281,7 +281,8 @@ size_t sl_poly2means_ws_bytes(int64_t C, int64_t n, int64_t D);
  * sklearn's k-means++ with 2 + int(ln k) local trials per further centre, Lloyd with relocation of every empty cluster
  * (ascending cluster id, farthest points first), score = 1 - clarity_score of the k centres.  h_rand is
  * (n_init, n_clusters - 1, sl_kmeans_trials(n_clusters)) float64: RandomState.uniform draws in sklearn's order.
- * State lives in the workspace (L2) rather than LDS: the fallback for what sl_poly2means does not cover. */
+ * The same procedure as sl_poly2means (csrc/kmeans.hip writes it once) with its state in the workspace (L2) rather than LDS:
+ * for what sl_poly2means does not cover. */
 int sl_kmeans_trials(int n_clusters);
 int sl_polykmeans(const float* d_V, int64_t C, int64_t n, int64_t D, int n_clusters, const int32_t* h_first_center, int n_init,
                   const double* h_rand, int replace_empty_clusters, double* d_out, int32_t* d_min_count, void* d_ws,

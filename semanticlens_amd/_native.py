@@ -1796,39 +1796,27 @@ def poly2means(V: torch.Tensor, first_center, rand, replace_empty_clusters: bool
             raise ValueError(f"n_samples={n} exceeds the device kernel's maximum of {POLYK_MAX_N} samples per component")
     if C == 0:
         return out
-    per_comp = int(lib().sl_polykmeans_ws_bytes(1, n, D, n_clusters, n_init)) if general else int(lib().sl_poly2means_ws_bytes(1, n, D))
-    chunk = max(1, min(C, POLYK_MAX_COMPONENTS, _poly_ws_budget() // max(per_comp, 1)))
+    # the storage variant (csrc/kmeans.hip): entry point family, the arguments only it takes (ws_bytes: after C, n, D; the call:
+    # after D), and whether the call still reads the host arrays of the draws after it returns
+    name, ws_extra, call_extra, reads_host_async = \
+        ("sl_polykmeans", (int(n_clusters), n_init), (int(n_clusters),), True) if general else ("sl_poly2means", (), (), False)
+    ws_bytes, entry = getattr(lib(), name + "_ws_bytes"), getattr(lib(), name if labels is None else name + "_labels")
+    chunk = max(1, min(C, POLYK_MAX_COMPONENTS, _poly_ws_budget() // max(int(ws_bytes(1, n, D, *ws_extra)), 1)))
     ws = None
     with _on(Vd.device):
         for c0 in range(0, C, chunk):
             cc = min(chunk, C - c0)
             Vc, oc, mc = Vd[c0:c0 + cc], out[c0:c0 + cc], mincnt[c0:c0 + cc]
             lc = labels[c0:c0 + cc] if labels is not None else None
-            if general:
-                nbytes = int(lib().sl_polykmeans_ws_bytes(cc, n, D, n_clusters, n_init))
-                if ws is None or ws.numel() < nbytes:
-                    ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=Vd.device)
-                args = (_ptr(Vc), cc, n, D, int(n_clusters), first_center.ctypes.data_as(_vp), n_init, rand.ctypes.data_as(_vp),
-                        1 if replace_empty_clusters else 0, _ptr(oc), _ptr(mc))
-                if lc is None:
-                    rc = lib().sl_polykmeans(*args, _ptr(ws), nbytes, _stream(Vd))
-                else:
-                    rc = lib().sl_polykmeans_labels(*args, _ptr(lc), _ptr(ws), nbytes, _stream(Vd))
+            nbytes = int(ws_bytes(cc, n, D, *ws_extra))
+            if ws is None or ws.numel() < nbytes:
+                ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=Vd.device)
+            rc = entry(_ptr(Vc), cc, n, D, *call_extra, first_center.ctypes.data_as(_vp), n_init, rand.ctypes.data_as(_vp),
+                       1 if replace_empty_clusters else 0, _ptr(oc), _ptr(mc), *(() if lc is None else (_ptr(lc),)), _ptr(ws), nbytes,
+                       _stream(Vd))
+            if reads_host_async:
                 torch.cuda.current_stream(Vd.device).synchronize()  # the draws were copied from host arrays owned by this call
-                _check(rc, "sl_polykmeans")
-            else:
-                nbytes = int(lib().sl_poly2means_ws_bytes(cc, n, D))
-                if ws is None or ws.numel() < nbytes:
-                    ws = torch.empty(nbytes, dtype=torch.uint8, device=Vd.device)
-                args = (_ptr(Vc), cc, n, D, first_center.ctypes.data_as(_vp), n_init, rand.ctypes.data_as(_vp),
-                        1 if replace_empty_clusters else 0, _ptr(oc), _ptr(mc))
-                if lc is None:
-                    rc = lib().sl_poly2means(*args, _ptr(ws), nbytes, _stream(Vd))
-                else:
-                    rc = lib().sl_poly2means_labels(*args, _ptr(lc), _ptr(ws), nbytes, _stream(Vd))
-                if rc == -3:
-                    raise NotImplementedError(lib().sl_last_error().decode())
-                _check(rc, "sl_poly2means")
+            _check(rc, name)
             if stats is not None:
                 _facet_stats_into(Vc, lc, n_clusters, *(t[c0:c0 + cc] for t in stats))
     return out

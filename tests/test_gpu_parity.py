@@ -1070,6 +1070,61 @@ def test_polysemanticity_chunks_components_and_reports_limits(monkeypatch):
     assert scores.polysemanticity_score(torch.zeros(0, 5, 4, device=DEV)).shape == (0,)
 
 
+def _k9_entry_point(V, first, rand, replace, general):
+    """(score, min_count, labels) of one K9 storage variant at k = 2, straight from its entry point: the min_count the kernel
+    decides the fallback by is not handed out by `_native.poly2means`."""
+    C, n, D = V.shape
+    lib, p = N.lib(), N._ptr
+    first, rand = np.ascontiguousarray(first, dtype=np.int32), np.ascontiguousarray(rand, dtype=np.float64)
+    score = torch.empty((C,), dtype=torch.float64, device=DEV)
+    mc = torch.empty((C,), dtype=torch.int32, device=DEV)
+    lab = torch.empty((C, n), dtype=torch.int32, device=DEV)
+    nbytes = int(lib.sl_polykmeans_ws_bytes(C, n, D, 2, len(first)) if general else lib.sl_poly2means_ws_bytes(C, n, D))
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=DEV)
+    tail = (first.ctypes.data_as(N._vp), len(first), rand.ctypes.data_as(N._vp), int(replace), p(score), p(mc), p(lab), p(ws), nbytes,
+            N._stream(V))
+    rc = lib.sl_polykmeans_labels(p(V), C, n, D, 2, *tail) if general else lib.sl_poly2means_labels(p(V), C, n, D, *tail)
+    torch.cuda.synchronize()
+    assert rc == 0
+    return score, mc, lab
+
+
+@pytest.mark.parametrize("C,n,D,kind", [(64, 20, 64, "random"), (64, 20, 64, "blobs"), (32, 5, 8, "random"), (16, 128, 16, "random"),
+                                        (20, 12, 16, "alldup")])
+def test_polysemanticity_storage_variants_agree(monkeypatch, C, n, D, kind):
+    """K9 is one procedure over two storage variants (csrc/kmeans.hip).  k = 2 as dispatched (LDS variant) and with the
+    workspace variant forced pick the same clustering: labels and min_count equal exactly, scores within 1e-9 — the closing
+    score's arithmetic differs between the variants, and 1e-9 is this file's "same clustering" bound.  "alldup": ten components
+    whose samples are all the same (the relocation's early return, an empty second cluster).  Measured: labels and min_count
+    equal on every component, largest score difference 6.7e-16; the two separate kernels this procedure replaced passed the
+    same five cases (4.4e-16), the all-duplicate one included."""
+    rng = np.random.RandomState(C + n + D)
+    V = rng.randn(C, n, D).astype(np.float32)
+    if kind == "blobs":
+        cen = rng.randn(C, 2, D).astype(np.float32) * 2
+        V = cen[np.arange(C)[:, None], rng.randint(0, 2, size=(C, n))] + 0.5 * V
+    if kind == "alldup":
+        V[:10, 1:] = V[:10, :1]
+    V = torch.from_numpy(V).to(DEV)
+    first, rand = scores.kmeans_draws(n, 10, 123, 2)
+    for replace in (True, False):
+        got = {}
+        for variant, max_n in (("lds", N.POLY2_MAX_N), ("workspace", 0)):
+            monkeypatch.setattr(N, "POLY2_MAX_N", max_n)
+            lab = torch.full((C, n), -1, dtype=torch.int32, device=DEV)
+            score = N.poly2means(V, first, rand, replace, n_clusters=2, labels=lab)
+            s2, mc, l2 = _k9_entry_point(V, first, rand, replace, general=variant == "workspace")
+            assert torch.equal(score, s2) and torch.equal(lab, l2), f"{variant}: the dispatch did not reach this variant's entry point"
+            got[variant] = (score.cpu().numpy(), mc.cpu().numpy(), lab.cpu().numpy())
+        monkeypatch.undo()
+        (sa, ma, la), (sb, mb, lb) = got["lds"], got["workspace"]
+        print(f"{kind} replace={replace}: labels differ on {int((la != lb).any(axis=1).sum())} components, min_count on "
+              f"{int((ma != mb).sum())}, max |score difference| {np.abs(sa - sb).max():.3g}")
+        assert np.array_equal(la, lb)
+        assert np.array_equal(ma, mb)
+        np.testing.assert_allclose(sa, sb, rtol=0, atol=1e-9)
+
+
 def test_probe_dict_uses_one_native_call_and_matches_per_layer():
     from semanticlens_amd.lens import _probe
 

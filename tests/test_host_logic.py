@@ -911,6 +911,18 @@ def test_rowseg_tile_header_on_the_host(tmp_path):
     assert "failures=0" in res.stdout
 
 
+def test_kmeans_layout_header_on_the_host(tmp_path):
+    """csrc/kmeans_layout.hpp compiled for the host: K9's workspace sizes on a table recorded from the size queries' former
+    formulas, each storage variant's carve-up ending at the size reported for it, and the LDS variant at n = 128 inside 160 KiB
+    (tests/native/kmeans_layout_check.cpp)."""
+    exe = tmp_path / "kmeans_layout_check"
+    subprocess.run(["g++", "-O2", "-std=c++17", "-Wall", "-Wextra", "-o", str(exe),
+                    str(ROOT / "tests" / "native" / "kmeans_layout_check.cpp")], check=True)
+    res = subprocess.run([str(exe)], capture_output=True, text=True)
+    assert res.returncode == 0, res.stdout + res.stderr
+    assert "failures=0" in res.stdout
+
+
 @pytest.mark.parametrize("R,n,chunk_rows", [(3, 10, 4), (3, 10, None), (1, 1, 1), (0, 5, None), (5, 0, None)])
 def test_row_probe_driver_walks_the_tiles_once_for_all_folds(monkeypatch, R, n, chunk_rows):
     """`_native._row_probe`, the walk under `topk_probe`, `softmax_probe` and `rank_probe`, with a fake cosine GEMM and recording

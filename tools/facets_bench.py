@@ -12,7 +12,10 @@
 Times are HIP-event times after warm-up; medians of ``--reps`` windows.  ``--size`` shrinks the component counts for a rehearsal;
 a figure taken below the default sizes is a figure of overheads.
 
-    python tools/facets_bench.py [--parent-tree DIR] [--out profiles/k21_facets_bench.txt]
+``--kc`` sets ``n_clusters`` (2 with at most 128 samples: K9's LDS variant; anything else: its workspace variant) and ``--shape
+C,n,D`` replaces the two layers by one shape, for all three measurements.
+
+    python tools/facets_bench.py [--parent-tree DIR] [--kc K] [--shape C,n,D] [--out profiles/k21_facets_bench.txt]
 """
 from __future__ import annotations
 
@@ -53,8 +56,10 @@ def alternate(torch, fns: dict, reps: int, warmup: int, inner: int) -> dict:
     return times
 
 
-def shapes(size):
-    return [(min(C, size) if size else C, n, D) for C, n, D in SHAPES]
+def shapes(args):
+    """The shapes to time: ``--shape`` alone when given, else the two layers; ``--size`` caps the component counts."""
+    todo = [tuple(int(x) for x in args.shape.split(","))] if args.shape else SHAPES
+    return [(min(C, args.size) if args.size else C, n, D) for C, n, D in todo]
 
 
 def child(args):
@@ -66,17 +71,17 @@ def child(args):
     from semanticlens_amd import scores
 
     dev = N.default_device()
-    for C, n, D in shapes(args.size):
+    for C, n, D in shapes(args):
         V = torch.randn(C, n, D, generator=torch.Generator().manual_seed(0)).to(dev)
-        t = alternate(torch, {"score": lambda: scores.polysemanticity_score(V)}, args.reps, args.warmup, 1)["score"]
-        digest = float(scores.polysemanticity_score(V).sum())
+        t = alternate(torch, {"score": lambda: scores.polysemanticity_score(V, n_clusters=args.kc)}, args.reps, args.warmup, 1)["score"]
+        digest = float(scores.polysemanticity_score(V, n_clusters=args.kc).sum())
         print(json.dumps({"shape": [C, n, D], "ms_median": round(median(t), 3), "ms_all": [round(x, 3) for x in t], "score_sum": digest}),
               flush=True)
 
 
 def run_child(tree, args):
     cmd = [sys.executable, str(Path(__file__).resolve()), "--child", "--tree", str(tree), "--reps", str(args.reps), "--warmup",
-           str(args.warmup), "--size", str(args.size)]
+           str(args.warmup), "--size", str(args.size), "--kc", str(args.kc)] + (["--shape", args.shape] if args.shape else [])
     out = subprocess.run(cmd, check=True, capture_output=True, text=True, timeout=600).stdout
     return [json.loads(line) for line in out.splitlines() if line.startswith("{")]
 
@@ -88,6 +93,8 @@ def main():
     ap.add_argument("--inner", type=int, default=50, help="launches per timed window of the two kernels")
     ap.add_argument("--rounds", type=int, default=3, help="child processes per tree for the parent comparison")
     ap.add_argument("--size", type=int, default=0, help="cap on the component counts (0: the full shapes)")
+    ap.add_argument("--kc", type=int, default=2, help="n_clusters (2: K9's LDS kernel up to 128 samples; else its general kernel)")
+    ap.add_argument("--shape", default=None, help="C,n,D: time this shape instead of the two layers")
     ap.add_argument("--parent-tree", default=None)
     ap.add_argument("--out", default=None)
     ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)
@@ -108,10 +115,10 @@ def main():
         for _ in range(args.rounds):
             for name, tree in (("parent", args.parent_tree), ("this", ROOT)):
                 runs[name].append(run_child(tree, args))
-        for i, shape in enumerate(shapes(args.size)):
+        for i, shape in enumerate(shapes(args)):
             meds = {name: [r[i]["ms_median"] for r in rs] for name, rs in runs.items()}
             sums = {r[i]["score_sum"] for rs in runs.values() for r in rs}
-            say({"what": "polysemanticity_score, this tree against the parent tree", "shape": shape,
+            say({"what": "polysemanticity_score, this tree against the parent tree", "shape": shape, "kc": args.kc,
                  "this_ms_medians_per_process": meds["this"], "parent_ms_medians_per_process": meds["parent"],
                  "this_ms": median(meds["this"]), "parent_ms": median(meds["parent"]),
                  "this_over_parent": round(median(meds["this"]) / median(meds["parent"]), 4),
@@ -125,8 +132,8 @@ def main():
     from semanticlens_amd import scores
 
     dev = N.default_device()
-    kc = 2
-    for C, n, D in shapes(args.size):
+    kc = args.kc
+    for C, n, D in shapes(args):
         V = torch.randn(C, n, D, generator=torch.Generator().manual_seed(0)).to(dev)
         f = scores.polysemanticity_facets(V, n_clusters=kc)
         labels = f.labels
