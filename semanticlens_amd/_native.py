@@ -1931,29 +1931,27 @@ def attention(qkv, B, T, H, head_dim, causal, out=None, out_split: Split | None 
     return out if out is not None else out_split
 
 
+def _attention_pool(name, q, q_stride, kv, B, T, H, head_dim, out):
+    W = H * head_dim
+    _need_f32(name, q, kv, out)
+    if out is None:
+        out = torch.empty((B, W), dtype=torch.float32, device=kv.device)
+    q_args = (_ptr(q),) if q_stride is None else (_ptr(q), q_stride)  # the C entry points differ in this argument only
+    with _on(kv.device):
+        rc = getattr(lib(), "sl_" + name)(*q_args, _ptr(kv), kv.stride(0), W, B, T, H, head_dim, _ptr(out), _stream(kv))
+    _check(rc, "sl_" + name)
+    return out
+
+
 def attention_pool(q, kv, B, T, H, head_dim, out=None):
     """One query per head against the keys / values of each image: ``q`` (H*head_dim) projected probe, ``kv`` (B*T, 2*W)
     rows ``[k | v]`` -> ``(B, W)``."""
-    W = H * head_dim
-    _need_f32("attention_pool", q, kv, out)
-    if out is None:
-        out = torch.empty((B, W), dtype=torch.float32, device=kv.device)
-    with _on(kv.device):
-        rc = lib().sl_attention_pool(_ptr(q), _ptr(kv), kv.stride(0), W, B, T, H, head_dim, _ptr(out), _stream(kv))
-    _check(rc, "sl_attention_pool")
-    return out
+    return _attention_pool("attention_pool", q, None, kv, B, T, H, head_dim, out)
 
 
 def attention_pool_q(q, kv, B, T, H, head_dim, out=None):
     """``attention_pool`` with one query per image: ``q`` (B, H*head_dim) -> ``(B, W)`` (CLIP-ResNet attention pool)."""
-    W = H * head_dim
-    _need_f32("attention_pool_q", q, kv, out)
-    if out is None:
-        out = torch.empty((B, W), dtype=torch.float32, device=kv.device)
-    with _on(kv.device):
-        rc = lib().sl_attention_pool_q(_ptr(q), q.stride(0), _ptr(kv), kv.stride(0), W, B, T, H, head_dim, _ptr(out), _stream(kv))
-    _check(rc, "sl_attention_pool_q")
-    return out
+    return _attention_pool("attention_pool_q", q, q.stride(0), kv, B, T, H, head_dim, out)
 
 
 def tokens_from_map(fmap, pos, out=None):

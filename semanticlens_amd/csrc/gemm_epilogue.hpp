@@ -1,7 +1,7 @@
 // Shared epilogue of the MFMA GEMM kernels (gemm_f32.hpp, gemm_bf16x3.hpp, gemm_8phase.hpp).
 // An epilogue object `epi` provides `column(col)` (per-column value: bias, inverse norm, ...) and
 // `store(row, col, acc, column_value)`.  One that ADDS A VALUE IT READS FROM MEMORY per element (the residual stream,
-// positional rows: encoder.hip LinearEpi) additionally exposes
+// positional rows: encoder_epilogue.hpp LinearEpi) additionally exposes
 //     static constexpr bool kFetches = true;   fetch(row, col);   store_fetched(row, col, acc, column_value, fetched)
 // with store(...) == store_fetched(..., fetch(row, col)) bit for bit.  The output may alias the memory that is read
 // (x += W h in place), so written element by element the compiler must keep every load behind the store in front of it:

@@ -67,7 +67,7 @@ def _first(obj, *names):
     raise AttributeError(f"none of {names} found on {type(obj).__name__}")
 
 
-_HEAD_DIMS = (32, 64, 72, 80, 88, 96, 104, 128)  # exactly what csrc/encoder.hip instantiates sl_attention / sl_attention_bf16x3 for
+_HEAD_DIMS = (32, 64, 72, 80, 88, 96, 104, 128)  # exactly csrc/encoder_attention.hip's SL_ATTENTION_HEAD_DIMS (sl_attention / sl_attention_bf16x3)
 
 
 def _ln(mod: nn.Module, device):
@@ -109,33 +109,123 @@ def _layer_scale(mod, device):
     return _f32(gamma, device)
 
 
+class _Layer:
+    """One linear layer: ``w`` the fp32 ``(N, K)`` weight, ``b`` the fp32 bias or None, ``op`` the weight as the tower's
+    arithmetic multiplies it (set by the arithmetic's ``hold``)."""
+
+    def __init__(self, w: torch.Tensor, b: torch.Tensor | None = None):
+        self.w, self.b, self.op = w, b, None
+
+    @classmethod
+    def of(cls, lin: nn.Linear, device):
+        """An ``nn.Linear``; a missing bias reads as zeros."""
+        b = _f32(lin.bias, device) if lin.bias is not None else torch.zeros(lin.out_features, dtype=torch.float32, device=device)
+        return cls(_f32(lin.weight, device), b)
+
+    @classmethod
+    def cat(cls, lins, device):
+        """Several ``nn.Linear`` over one input as one layer: weight rows and biases concatenated (``[q | k | v]``, ``[k | v]``)."""
+        parts = [cls.of(lin, device) for lin in lins]
+        return cls(torch.cat([p.w for p in parts]).contiguous(), torch.cat([p.b for p in parts]).contiguous())
+
+    def scaled(self, gamma):
+        """LayerScale folded into the projection it follows: gamma * (W x + b) = (gamma W) x + gamma b."""
+        return self if gamma is None else _Layer((self.w * gamma[:, None]).contiguous(), (self.b * gamma).contiguous())
+
+
+class _F32:
+    """The towers' arithmetic under ``gemm="f32"``: weights and GEMM operands are fp32 tensors, the linear layers run on the
+    fp32-input MFMA GEMM (``N.linear``), attention on ``sl_attention``.  Each step names its destination as ``out``; a step
+    that is asked for ``as_operand`` leaves what the next GEMM reads — here the same fp32 tensor."""
+
+    @staticmethod
+    def hold(*layers):
+        for layer in layers:
+            if layer is not None:
+                layer.op = layer.w
+
+    @staticmethod
+    def buffer(rows: int, cols: int, device):
+        return torch.empty((rows, cols), dtype=torch.float32, device=device)
+
+    @staticmethod
+    def operand(x: torch.Tensor):
+        return x
+
+    @staticmethod
+    def layernorm(x, ln, out=None):
+        return N.layernorm(x, *ln, out=out)
+
+    @staticmethod
+    def linear(x, layer: _Layer, act=N.SL_ACT_NONE, residual=None, out=None, as_operand=False, scatter=None, rowadd=None):
+        return N.linear(x, layer.op, layer.b, act=act, residual=residual, out=out, scatter=scatter, rowadd=rowadd)
+
+    @staticmethod
+    def attention(qkv, B, T, heads, head_dim, causal, out, as_operand=True):
+        return N.attention(qkv, B, T, heads, head_dim, causal, out=out)
+
+    @staticmethod
+    def patchify(img, patch: int):
+        return N.patchify(img, patch)
+
+
+class _Bf16x3:
+    """The towers' arithmetic under ``gemm="bf16x3"``: weights are split once (``N.Split.of``), activations leave the
+    producing kernel in split form (``as_operand``: into the ``N.Split`` given as ``out``, or a fresh one), the linear layers
+    run as split-bf16 x3 GEMMs (``N.linear3``) and attention as ``sl_attention_bf16x3``.  Results that are not the next
+    GEMM's operand (the residual stream, qkv, pooled rows) stay fp32."""
+
+    @staticmethod
+    def hold(*layers):
+        for layer in layers:
+            if layer is not None and layer.op is None:
+                layer.op = N.Split.of(layer.w)
+
+    @staticmethod
+    def buffer(rows: int, cols: int, device):
+        return N.Split(rows, cols, device)
+
+    @staticmethod
+    def operand(x: torch.Tensor):
+        return N.Split.of(x)
+
+    @staticmethod
+    def layernorm(x, ln, out=None):
+        return N.layernorm(x, *ln, out_split=out if out is not None else N.Split(x.shape[0], x.shape[1], x.device))
+
+    @staticmethod
+    def linear(x, layer: _Layer, act=N.SL_ACT_NONE, residual=None, out=None, as_operand=False, scatter=None, rowadd=None):
+        if as_operand:  # e.g. the GELU output leaves as split bf16
+            return N.linear3(x, layer.op, layer.b, act=act, out_split=out if out is not None else N.Split(x.shape[0], layer.w.shape[0], x.buf.device))
+        return N.linear3(x, layer.op, layer.b, act=act, residual=residual, out=out, scatter=scatter, rowadd=rowadd)
+
+    @staticmethod
+    def attention(qkv, B, T, heads, head_dim, causal, out, as_operand=True):
+        """Both products split-bf16 x3.  ``as_operand=False``: a fresh fp32 result (``out`` is left alone), for the pooled last
+        block, which splits the rows it gathers instead of the whole matrix."""
+        if as_operand:
+            return N.attention(qkv, B, T, heads, head_dim, causal, out_split=out, bf16x3=True)
+        return N.attention(qkv, B, T, heads, head_dim, causal, bf16x3=True)
+
+    @staticmethod
+    def patchify(img, patch: int):
+        B, C, Hi, Wi = img.shape
+        return N.patchify(img, patch, out_split=N.Split(B * (Hi // patch) * (Wi // patch), C * patch * patch, img.device))
+
+
+_ARITHMETICS = {"f32": _F32, "bf16x3": _Bf16x3}
+
+
 class _BlockWeights:
-    """Weights of one pre-LN residual block as flat fp32 device tensors, whatever module layout they were read from:
-    ``x += W_o attn(LN1(x) W_qkv^T) ; x += W_pr act(W_fc LN2(x))`` with the in-projection packed ``[q | k | v]``."""
+    """Weights of one pre-LN residual block, whatever module layout they were read from:
+    ``x += W_o attn(LN1(x) W_qkv^T) ; x += W_pr act(W_fc LN2(x))`` with the in-projection packed ``[q | k | v]``.  The
+    readers below set ``ln1``, ``ln2`` and the four `_Layer` ``qkv``, ``o``, ``fc``, ``pr``."""
 
     def __init__(self, width: int, heads: int, act: int):
         self.width, self.heads, self.act = int(width), int(heads), act
         self.head_dim = self.width // self.heads
         if self.head_dim not in _HEAD_DIMS or self.head_dim * self.heads != self.width:
             raise ValueError(f"head_dim {self.head_dim} is not supported (built: {_HEAD_DIMS})")
-
-    def scale_branches(self, g_attn, g_mlp):
-        """Fold LayerScale into the projection it follows: gamma * (W x + b) = (gamma W) x + gamma b."""
-        if g_attn is not None:
-            self.w_o, self.b_o = (self.w_o * g_attn[:, None]).contiguous(), (self.b_o * g_attn).contiguous()
-        if g_mlp is not None:
-            self.w_pr, self.b_pr = (self.w_pr * g_mlp[:, None]).contiguous(), (self.b_pr * g_mlp).contiguous()
-        return self
-
-    def finish(self, split: bool):
-        if split and not hasattr(self, "s_qkv"):
-            self.s_qkv, self.s_o = N.Split.of(self.w_qkv), N.Split.of(self.w_o)
-            self.s_fc, self.s_pr = N.Split.of(self.w_fc), N.Split.of(self.w_pr)
-        return self
-
-
-def _bias(lin: nn.Linear, device):
-    return _f32(lin.bias, device) if lin.bias is not None else torch.zeros(lin.out_features, dtype=torch.float32, device=device)
 
 
 def _read_mha_block(blk: nn.Module, device) -> _BlockWeights:
@@ -152,11 +242,11 @@ def _read_mha_block(blk: nn.Module, device) -> _BlockWeights:
         raise TypeError("expected an MLP of Linear, activation, Linear")
     w = _BlockWeights(attn.embed_dim, attn.num_heads, _act_code(others[0]))
     w.ln1, w.ln2 = _ln(blk.ln_1, device), _ln(blk.ln_2, device)
-    w.w_qkv, w.b_qkv = _f32(attn.in_proj_weight, device), _f32(attn.in_proj_bias, device)
-    w.w_o, w.b_o = _f32(attn.out_proj.weight, device), _bias(attn.out_proj, device)
-    w.w_fc, w.b_fc = _f32(linears[0].weight, device), _bias(linears[0], device)
-    w.w_pr, w.b_pr = _f32(linears[1].weight, device), _bias(linears[1], device)
-    return w.scale_branches(_layer_scale(getattr(blk, "ls_1", None), device), _layer_scale(getattr(blk, "ls_2", None), device))
+    w.qkv = _Layer(_f32(attn.in_proj_weight, device), _f32(attn.in_proj_bias, device))
+    w.o = _Layer.of(attn.out_proj, device).scaled(_layer_scale(getattr(blk, "ls_1", None), device))
+    w.fc = _Layer.of(linears[0], device)
+    w.pr = _Layer.of(linears[1], device).scaled(_layer_scale(getattr(blk, "ls_2", None), device))
+    return w
 
 
 def _read_hf_siglip_block(blk: nn.Module, heads: int, act: int, device) -> _BlockWeights:
@@ -166,11 +256,8 @@ def _read_hf_siglip_block(blk: nn.Module, heads: int, act: int, device) -> _Bloc
     a = blk.self_attn
     w = _BlockWeights(a.q_proj.in_features, heads, act)
     w.ln1, w.ln2 = _ln(blk.layer_norm1, device), _ln(blk.layer_norm2, device)
-    w.w_qkv = torch.cat([_f32(p.weight, device) for p in (a.q_proj, a.k_proj, a.v_proj)], 0).contiguous()
-    w.b_qkv = torch.cat([_bias(p, device) for p in (a.q_proj, a.k_proj, a.v_proj)], 0).contiguous()
-    w.w_o, w.b_o = _f32(a.out_proj.weight, device), _bias(a.out_proj, device)
-    w.w_fc, w.b_fc = _f32(blk.mlp.fc1.weight, device), _bias(blk.mlp.fc1, device)
-    w.w_pr, w.b_pr = _f32(blk.mlp.fc2.weight, device), _bias(blk.mlp.fc2, device)
+    w.qkv = _Layer.cat((a.q_proj, a.k_proj, a.v_proj), device)
+    w.o, w.fc, w.pr = _Layer.of(a.out_proj, device), _Layer.of(blk.mlp.fc1, device), _Layer.of(blk.mlp.fc2, device)
     return w
 
 
@@ -186,82 +273,61 @@ def _read_timm_block(blk: nn.Module, device) -> _BlockWeights:
         raise TypeError("timm Mlp with an inner norm is not built")
     w = _BlockWeights(a.qkv.in_features, a.num_heads, _act_code(blk.mlp.act))
     w.ln1, w.ln2 = _ln(blk.norm1, device), _ln(blk.norm2, device)
-    w.w_qkv, w.b_qkv = _f32(a.qkv.weight, device), _bias(a.qkv, device)
-    w.w_o, w.b_o = _f32(a.proj.weight, device), _bias(a.proj, device)
-    w.w_fc, w.b_fc = _f32(blk.mlp.fc1.weight, device), _bias(blk.mlp.fc1, device)
-    w.w_pr, w.b_pr = _f32(blk.mlp.fc2.weight, device), _bias(blk.mlp.fc2, device)
-    return w.scale_branches(_layer_scale(getattr(blk, "ls1", None), device), _layer_scale(getattr(blk, "ls2", None), device))
+    w.qkv = _Layer.of(a.qkv, device)
+    w.o = _Layer.of(a.proj, device).scaled(_layer_scale(getattr(blk, "ls1", None), device))
+    w.fc = _Layer.of(blk.mlp.fc1, device)
+    w.pr = _Layer.of(blk.mlp.fc2, device).scaled(_layer_scale(getattr(blk, "ls2", None), device))
+    return w
 
 
-def _project(pooled: torch.Tensor, w: torch.Tensor | None, b: torch.Tensor | None, s_w) -> torch.Tensor:
-    """The tower's output projection of the pooled rows.  With ``s_w`` (the weight as a split matrix: split mode) it runs in the
-    arithmetic of the blocks (``linear3``: a (B, W) x (D, W) product is a few tiles, which the small-grid kernel walks in
-    ~6 us; the fp32-MFMA kernel took 65)."""
-    if w is None:
-        return pooled
-    if s_w is None:
-        return N.linear(pooled, w, b)
-    return N.linear3(N.Split.of(pooled), s_w, b)
+def _project(ar, pooled: torch.Tensor, layer: _Layer | None) -> torch.Tensor:
+    """The tower's output projection of the pooled rows, in the arithmetic of the blocks (split mode: a (B, W) x (D, W)
+    product is a few tiles, which the small-grid kernel walks in ~6 us; the fp32-MFMA kernel took 65)."""
+    return pooled if layer is None else ar.linear(ar.operand(pooled), layer)
 
 
 class _Tower:
-    """L residual blocks over a (B*T, W) fp32 token matrix (the residual stream stays fp32 in both modes)."""
+    """L residual blocks over a (B*T, W) fp32 token matrix (the residual stream stays fp32 in both arithmetics)."""
 
-    def __init__(self, blocks: list, split: bool):
-        """``blocks``: `_BlockWeights` in execution order (built by one of the layout readers below)."""
+    def __init__(self, blocks: list, ar):
+        """``blocks``: `_BlockWeights` in execution order (built by one of the layout readers above); ``ar``: `_F32` or `_Bf16x3`."""
         if not blocks:
             raise TypeError("the tower has no residual blocks")
-        self.split = split
-        self.blocks = [b.finish(split) for b in blocks]
+        self.ar, self.blocks = ar, blocks
+        for b in blocks:
+            ar.hold(b.qkv, b.o, b.fc, b.pr)
         self.width = self.blocks[0].width
         self.heads = self.blocks[0].heads
+
+    def _after_attention(self, blk, x, att, h=None, hid=None):
+        """``x += out_proj(att)``, then ``x += c_proj(act(c_fc(LN2(x))))``, in place on the rows ``x`` (all of them, or the
+        pooled ones); ``h`` / ``hid``: operand buffers to reuse."""
+        ar = self.ar
+        ar.linear(att, blk.o, residual=x, out=x)
+        h = ar.layernorm(x, blk.ln2, out=h)
+        hid = ar.linear(h, blk.fc, act=blk.act, out=hid, as_operand=True)
+        return ar.linear(hid, blk.pr, residual=x, out=x)
 
     def forward(self, x: torch.Tensor, B: int, T: int, causal: bool, pool_rows: torch.Tensor | None = None) -> torch.Tensor:
         """Runs the blocks over ``x`` in place.  ``pool_rows`` (B int64 row indices): only those rows of the final
         residual stream are needed (class token / end-of-text token), so the last block stops being computed for
         the other rows after its attention (keys and values still come from every token) and ``(B, W)`` is returned.
         Each GEMM row depends on its own input row only, so the pooled rows are bit-identical either way."""
+        ar = self.ar
         M, W = x.shape
-        F = self.blocks[0].w_fc.shape[0]
         qkv = torch.empty((M, 3 * W), dtype=torch.float32, device=x.device)
-        last = len(self.blocks) - 1
-        if self.split:
-            h, att, hid = N.Split(M, W, x.device), N.Split(M, W, x.device), N.Split(M, F, x.device)
-            for i, blk in enumerate(self.blocks):
-                N.layernorm(x, *blk.ln1, out_split=h)
-                N.linear3(h, blk.s_qkv, blk.b_qkv, out=qkv)
-                if i == last and pool_rows is not None:
-                    att32 = N.attention(qkv, B, T, blk.heads, blk.head_dim, causal, bf16x3=True)
-                    xp = N.gather_rows(x, pool_rows, check=False)
-                    N.linear3(N.Split.of(N.gather_rows(att32, pool_rows, check=False)), blk.s_o, blk.b_o, residual=xp, out=xp)
-                    hp = N.layernorm(xp, *blk.ln2, out_split=N.Split(B, W, x.device))
-                    hidp = N.linear3(hp, blk.s_fc, blk.b_fc, act=blk.act, out_split=N.Split(B, F, x.device))
-                    N.linear3(hidp, blk.s_pr, blk.b_pr, residual=xp, out=xp)
-                    return xp
-                N.attention(qkv, B, T, blk.heads, blk.head_dim, causal, out_split=att, bf16x3=True)  # both products split-bf16 x3
-                N.linear3(att, blk.s_o, blk.b_o, residual=x, out=x)  # x += out_proj(attn)
-                N.layernorm(x, *blk.ln2, out_split=h)
-                N.linear3(h, blk.s_fc, blk.b_fc, act=blk.act, out_split=hid)  # GELU output leaves as split bf16
-                N.linear3(hid, blk.s_pr, blk.b_pr, residual=x, out=x)  # x += c_proj(gelu(c_fc))
-            return x if pool_rows is None else N.gather_rows(x, pool_rows, check=False)
-        h = torch.empty_like(x)
-        att = torch.empty_like(x)
-        hid = torch.empty((M, F), dtype=torch.float32, device=x.device)
-        for i, blk in enumerate(self.blocks):
-            N.layernorm(x, *blk.ln1, out=h)
-            N.linear(h, blk.w_qkv, blk.b_qkv, out=qkv)
-            N.attention(qkv, B, T, blk.heads, blk.head_dim, causal, out=att)
-            if i == last and pool_rows is not None:
+        h, att, hid = ar.buffer(M, W, x.device), ar.buffer(M, W, x.device), ar.buffer(M, self.blocks[0].fc.w.shape[0], x.device)
+        for blk in self.blocks:
+            ar.layernorm(x, blk.ln1, out=h)
+            ar.linear(h, blk.qkv, out=qkv)
+            if blk is self.blocks[-1] and pool_rows is not None:
+                # attention's fp32 rows are gathered first and only those become an operand
+                att32 = ar.attention(qkv, B, T, blk.heads, blk.head_dim, causal, out=att, as_operand=False)
                 xp = N.gather_rows(x, pool_rows, check=False)
-                N.linear(N.gather_rows(att, pool_rows, check=False), blk.w_o, blk.b_o, residual=xp, out=xp)
-                hp = N.layernorm(xp, *blk.ln2)
-                N.linear(N.linear(hp, blk.w_fc, blk.b_fc, act=blk.act), blk.w_pr, blk.b_pr, residual=xp, out=xp)
-                return xp
-            N.linear(att, blk.w_o, blk.b_o, residual=x, out=x)
-            N.layernorm(x, *blk.ln2, out=h)
-            N.linear(h, blk.w_fc, blk.b_fc, act=blk.act, out=hid)
-            N.linear(hid, blk.w_pr, blk.b_pr, residual=x, out=x)
-        return x if pool_rows is None else N.gather_rows(x, pool_rows, check=False)
+                return self._after_attention(blk, xp, ar.operand(N.gather_rows(att32, pool_rows, check=False)))
+            ar.attention(qkv, B, T, blk.heads, blk.head_dim, causal, out=att)
+            self._after_attention(blk, x, att, h, hid)
+        return x
 
 
 # ---- a batch as several chunks on several HIP streams (off by default) ---------------------------------------------------
@@ -314,7 +380,7 @@ class NativeResNetVision:
     tokens to the queries, ``sl_attention_pool_q`` attends with one query per image and head, and ``c_proj`` maps to the
     joint space.  Same arithmetic as ``attnpool.forward`` (multi_head_attention_forward with separate projection weights)."""
 
-    def __init__(self, visual: nn.Module, device, split: bool):
+    def __init__(self, visual: nn.Module, device):
         pool = visual.attnpool
         for name in ("positional_embedding", "q_proj", "k_proj", "v_proj", "c_proj", "num_heads"):
             if not hasattr(pool, name):
@@ -326,20 +392,14 @@ class NativeResNetVision:
         if self.head_dim * self.heads != W or self.head_dim % 4 or self.head_dim > 128:
             raise ValueError(f"attention pool: head_dim {self.head_dim} (a multiple of 4 up to 128)")
         self.pos = _f32(pool.positional_embedding, device)  # (HW + 1, W)
-        self.w_kv = torch.cat([_f32(pool.k_proj.weight, device), _f32(pool.v_proj.weight, device)]).contiguous()  # (2W, W): rows [k | v]
-        self.b_kv = torch.cat([_bias(pool.k_proj, device), _bias(pool.v_proj, device)]).contiguous()
-        self.w_q, self.b_q = _f32(pool.q_proj.weight, device), _bias(pool.q_proj, device)
-        self.w_c, self.b_c = _f32(pool.c_proj.weight, device), _bias(pool.c_proj, device)
+        self.kv = _Layer.cat((pool.k_proj, pool.v_proj), device)  # (2W, W): rows [k | v]
+        self.q, self.c = _Layer.of(pool.q_proj, device), _Layer.of(pool.c_proj, device)
         # The head's four projections run on the fp32-MFMA GEMM (`N.linear`) in EVERY `gemm` mode.  A trunk hands the pool
         # tokens of magnitude ~20, its softmax logits are in the hundreds, and a 3-product bf16 split (per-product relative
         # error 2^-16..2^-17) then moves the attention weights by ~0.5 %: 1.1e-3 absolute on features of scale 22, 6x torch's
         # own fp32 distance from float64 (round-4 driver run).  The GEMMs are (B*50) x 4096 x 2048 at most: microseconds
         # beside the convolutional trunk, so the split buys nothing here.
-        self.split = False
-        del split
-
-    def _linear(self, x, w, b):
-        return N.linear(x, w, b)
+        _F32.hold(self.kv, self.q, self.c)
 
     def trunk(self, img: torch.Tensor) -> torch.Tensor:
         """``(B, C, h, w)`` output of ``layer4`` — the model's own forward with the attention pool taken out."""
@@ -365,10 +425,10 @@ class NativeResNetVision:
             raise ValueError(f"trunk output {tuple(fmap.shape)} does not match the attention pool ({self.pos.shape[0] - 1} positions of width {self.width})")
         tokens = N.tokens_from_map(fmap, self.pos)  # (B, T, W), row 0 = mean token
         rows = tokens.reshape(B * T, C)
-        kv = self._linear(rows, self.w_kv, self.b_kv)  # (B*T, 2W)
-        q = self._linear(tokens[:, 0].contiguous(), self.w_q, self.b_q)  # (B, W)
+        kv = _F32.linear(rows, self.kv)  # (B*T, 2W)
+        q = _F32.linear(tokens[:, 0].contiguous(), self.q)  # (B, W)
         pooled = N.attention_pool_q(q, kv, B, T, self.heads, self.head_dim)
-        return self._linear(pooled, self.w_c, self.b_c)
+        return _F32.linear(pooled, self.c)
 
 
 class NativeVisionTower:
@@ -376,7 +436,7 @@ class NativeVisionTower:
     ``"tok"`` (class token) or ``"avg"`` (mean of the patch tokens); ``ln_after_pool`` = open_clip's ``final_ln_after_pool``;
     ``ln_pre`` may be absent (``no_ln_pre``), ``proj`` too."""
 
-    def __init__(self, visual: nn.Module, blocks, device, split: bool, pool: str = "tok", ln_after_pool: bool = False):
+    def __init__(self, visual: nn.Module, blocks, device, ar, pool: str = "tok", ln_after_pool: bool = False):
         conv = visual.conv1
         if conv.bias is not None or conv.kernel_size != conv.stride:
             raise TypeError("NativeClip expects a bias-free patch embedding with stride == kernel size")
@@ -384,7 +444,7 @@ class NativeVisionTower:
             raise TypeError(f"visual.pool_type={pool!r}: only 'tok' and 'avg' are built")
         self.patch = conv.kernel_size[0]
         self.width = conv.out_channels
-        self.w_patch = _f32(conv.weight.reshape(self.width, -1), device)  # (W, C*P*P)
+        self.patch_embed = _Layer(_f32(conv.weight.reshape(self.width, -1), device))  # (W, C*P*P)
         self.cls = _f32(visual.class_embedding, device)
         self.pos = _f32(_first(visual, "positional_embedding", "positional_embedding_v"), device)
         self.ln_pre = None if _is_identity(visual.ln_pre) else _ln(visual.ln_pre, device)
@@ -392,12 +452,10 @@ class NativeVisionTower:
         proj = getattr(visual, "proj", None)
         if proj is None:
             proj = getattr(visual, "proj_v", None)
-        self.w_proj = _f32(proj.t(), device) if proj is not None else None  # features = x @ proj -> Linear weight (D, W)
-        self.s_proj = N.Split.of(self.w_proj) if split and self.w_proj is not None else None
-        self.split = split
-        if split:
-            self.s_patch = N.Split.of(self.w_patch)
-        self.tower = _Tower([_read_mha_block(b, device) for b in blocks], split)
+        self.proj = _Layer(_f32(proj.t(), device)) if proj is not None else None  # features = x @ proj -> Linear weight (D, W)
+        self.ar = ar
+        ar.hold(self.patch_embed, self.proj)
+        self.tower = _Tower([_read_mha_block(b, device) for b in blocks], ar)
         self.pool, self.ln_after_pool = pool, bool(ln_after_pool)
         self.pool_shortcut = True  # last block: out-proj / MLP for the class-token rows only (see _Tower.forward)
 
@@ -419,12 +477,7 @@ class NativeVisionTower:
         W = self.width
         x = torch.empty((B * T, W), dtype=torch.float32, device=img.device)
         # patch embedding GEMM; its epilogue scatters row (b, p) to token row b*T + 1 + p and adds pos[1 + p]
-        if self.split:
-            patches = N.patchify(img, self.patch, out_split=N.Split(B * n_patch, self.w_patch.shape[1], img.device))
-            N.linear3(patches, self.s_patch, out=x, scatter=(n_patch, T, 1), rowadd=self.pos)
-        else:
-            patches = N.patchify(img, self.patch)
-            N.linear(patches, self.w_patch, out=x, scatter=(n_patch, T, 1), rowadd=self.pos)
+        self.ar.linear(self.ar.patchify(img, self.patch), self.patch_embed, out=x, scatter=(n_patch, T, 1), rowadd=self.pos)
         N.broadcast_row(self.cls, self.pos[0], B, T * W, x)  # token 0 = class embedding + pos[0]
         h = N.layernorm(x, *self.ln_pre) if self.ln_pre is not None else x
         if self.pool == "tok":
@@ -443,7 +496,7 @@ class NativeVisionTower:
             N.reduce_tokens(h.view(B, T, W)[:, 1:], N.SL_TOK_MEAN, 0, None, pooled)
             if self.ln_after_pool:
                 pooled = N.layernorm(pooled, *self.ln_post)
-        return _project(pooled, self.w_proj, None, self.s_proj)
+        return _project(self.ar, pooled, self.proj)
 
 
 class NativeTextTower:
@@ -452,7 +505,7 @@ class NativeTextTower:
     token (``"argmax"``: CLIP's tokenizer gives it the highest id), the first or the last position, then the projection
     (a matrix, an ``nn.Linear`` with bias, or none)."""
 
-    def __init__(self, model: nn.Module, blocks, device, split: bool, pool: str = "argmax", causal: bool = True):
+    def __init__(self, model: nn.Module, blocks, device, ar, pool: str = "argmax", causal: bool = True):
         if pool not in ("argmax", "first", "last"):
             raise TypeError(f"text pool_type={pool!r}: only 'argmax', 'first' and 'last' are built")
         if getattr(model, "cls_emb", None) is not None:
@@ -463,13 +516,13 @@ class NativeTextTower:
         proj = getattr(model, "text_projection", None)
         if proj is None:
             proj = getattr(model, "proj_t", None)
-        self.b_proj = None
         if isinstance(proj, nn.Linear):
-            self.w_proj, self.b_proj = _f32(proj.weight, device), (_f32(proj.bias, device) if proj.bias is not None else None)
+            self.proj = _Layer(_f32(proj.weight, device), _f32(proj.bias, device) if proj.bias is not None else None)
         else:
-            self.w_proj = _f32(proj.t(), device) if proj is not None else None
-        self.s_proj = N.Split.of(self.w_proj) if split and self.w_proj is not None else None
-        self.tower = _Tower([_read_mha_block(b, device) for b in blocks], split)
+            self.proj = _Layer(_f32(proj.t(), device)) if proj is not None else None
+        self.ar = ar
+        ar.hold(self.proj)
+        self.tower = _Tower([_read_mha_block(b, device) for b in blocks], ar)
         self.pool, self.causal = pool, bool(causal)
         self.truncate = True  # skip the positions after the batch's last end-of-text token (see __call__)
         self.pool_shortcut = True  # last block: out-proj / MLP for the pooled rows only
@@ -500,7 +553,23 @@ class NativeTextTower:
         else:
             picked = N.gather_rows(self.tower.forward(x, B, T, causal=self.causal), rows, check=False)
         pooled = N.layernorm(picked, *self.ln_final)
-        return _project(pooled, self.w_proj, self.b_proj, self.s_proj)
+        return _project(self.ar, pooled, self.proj)
+
+    @property
+    def b_proj(self):
+        """The projection's bias: None for a matrix projection (``CLIP``), set for ``TextTransformer``'s ``nn.Linear``."""
+        return self.proj.b if self.proj is not None else None
+
+
+def _open_clip_text(model):
+    """open_clip's text tower of ``model``: its members sit on the model itself (``CLIP``) or under ``.text``
+    (``CustomTextCLIP``).  Returns that module and `NativeTextTower`'s arguments for it — None when it is not open_clip's
+    ``TextTransformer`` layout (``transformer.resblocks``), which each caller refuses in its own words."""
+    text = model.text if hasattr(getattr(model, "text", None), "transformer") else model
+    if not hasattr(getattr(text, "transformer", None), "resblocks"):
+        return text, None
+    pool = getattr(text, "pool_type", None) or getattr(model, "text_pool_type", "argmax")
+    return text, dict(blocks=text.transformer.resblocks, pool=pool, causal=getattr(text, "attn_mask", None) is not None)
 
 
 def _require_clip_layout(model):
@@ -518,64 +587,26 @@ def _require_clip_layout(model):
         raise TypeError("NativeClip does not implement this open_clip variant: " + "; ".join(sorted(set(problems))))
 
 
-class NativeClip(AbstractVLM):
-    """``AbstractVLM`` running ``base``'s CLIP towers on HIP kernels; ``base`` keeps tokenizer + preprocessing."""
+class _NativeVLM(AbstractVLM):
+    """What the native wrappers share: ``base`` keeps tokenizer + preprocessing, `_read_towers` (the subclass) reads
+    ``base.model`` into ``self.vision`` / ``self.text``."""
 
-    # The embed stage of the concept-DB build may hold preprocessed batches back until this many images are there: the
-    # towers' GEMMs reach their rate from a few thousand rows, and an embedding does not depend on its batch (bit for bit).
-    embed_accumulate = 256
+    _name = "native-"
 
     def __init__(self, base, device=None, gemm: str = "bf16x3", preprocess=None):
         """``preprocess``: ``None`` keeps ``base.preprocess`` (host transform, as upstream); a
         ``DevicePreprocess`` (or ``"device"`` to derive one from ``base.preprocessor``) runs resize / crop /
         normalise for the whole batch on the device (K12)."""
-        if gemm not in ("bf16x3", "f32"):
+        if gemm not in _ARITHMETICS:
             raise ValueError("gemm must be 'bf16x3' or 'f32'")
-        split = gemm == "bf16x3"
         self.base = base
-        model = base.model
-        dev = torch.device(device) if device is not None else next(model.parameters()).device
+        dev = torch.device(device) if device is not None else next(base.model.parameters()).device
         if dev.type != "cuda":
             dev = N.default_device()
         self._device = dev
         base.to(dev)
-        visual = getattr(model, "visual", None)
-        if visual is not None and hasattr(visual, "attnpool") and hasattr(visual, "layer4"):
-            # CLIP ResNet (open_clip ModifiedResNet): conv trunk on PyTorch, attention pool + projection on the kernels;
-            # the text tower in open_clip's layout (members on the model) or synth's (`model.text.blocks`)
-            self.vision = NativeResNetVision(visual, dev, split)
-            if hasattr(model, "transformer") and hasattr(model.transformer, "resblocks"):
-                pool = getattr(model, "text_pool_type", "argmax")
-                self.text = NativeTextTower(model, model.transformer.resblocks, dev, split, pool=pool,
-                                            causal=getattr(model, "attn_mask", None) is not None)
-            elif hasattr(getattr(model, "text", None), "blocks"):
-                self.text = NativeTextTower(model, model.text.blocks, dev, split)
-            else:
-                raise TypeError("NativeClip: CLIP-ResNet image tower with a text tower that is neither open_clip's nor synth's layout")
-        elif visual is not None and hasattr(visual, "conv1") and hasattr(visual, "transformer"):
-            # open_clip CLIP: `visual` is the whole image tower, the text tower's members sit on the model itself
-            # (CustomTextCLIP keeps them under `.text`)
-            _require_clip_layout(model)
-            self.vision = NativeVisionTower(visual, visual.transformer.resblocks, dev, split, pool=getattr(visual, "pool_type", "tok"),
-                                            ln_after_pool=getattr(visual, "final_ln_after_pool", False))
-            text = model.text if hasattr(model, "text") and hasattr(model.text, "transformer") else model
-            if not hasattr(getattr(text, "transformer", None), "resblocks"):
-                # e.g. open_clip's CustomTextCLIP around a Hugging Face text encoder: `.text.transformer` is an HF model
-                raise TypeError(f"NativeClip reads open_clip's TextTransformer layout (`transformer.resblocks`); the text tower is "
-                                f"{type(text).__name__} around {type(getattr(text, 'transformer', None)).__name__} — run this model "
-                                "through its own torch modules (OpenClip without .native())")
-            pool = getattr(text, "pool_type", None) or getattr(model, "text_pool_type", "argmax")
-            self.text = NativeTextTower(text, text.transformer.resblocks, dev, split, pool=pool,
-                                        causal=getattr(text, "attn_mask", None) is not None)
-        elif visual is not None and hasattr(model, "conv1") and hasattr(visual, "blocks"):
-            # synth._ClipModel: embedding members on the model, block stacks in .visual / .text
-            self.vision = NativeVisionTower(_SynthVisual(model), visual.blocks, dev, split)
-            self.text = NativeTextTower(model, model.text.blocks, dev, split)
-        else:
-            found = type(visual).__name__ if visual is not None else "no `visual` member"
-            raise TypeError(f"NativeClip reads open_clip's CLIP / VisionTransformer layout; {type(model).__name__} has {found} "
-                            "(timm trunks: NativeSigLip; convolutional / hybrid towers such as MobileCLIP are not built)")
-        self.name = f"native-{gemm}-" + getattr(base, "name", type(base).__name__)
+        self._read_towers(base.model, dev, _ARITHMETICS[gemm])
+        self.name = f"{self._name}{gemm}-" + getattr(base, "name", type(base).__name__)
         if preprocess == "device":
             from semanticlens_amd.foundation_models.preprocess import DevicePreprocess
 
@@ -593,7 +624,7 @@ class NativeClip(AbstractVLM):
 
     def to(self, device):
         if torch.device(device).type != "cuda":
-            raise N.NativeLibraryError("NativeClip runs on a HIP device only")
+            raise N.NativeLibraryError(f"{type(self).__name__} runs on a HIP device only")
         return self
 
     def encode_image(self, img):
@@ -612,6 +643,48 @@ class NativeClip(AbstractVLM):
         return self.base.tokenize(txt, *args, **kwargs)
 
 
+class NativeClip(_NativeVLM):
+    """``AbstractVLM`` running ``base``'s CLIP towers on HIP kernels; ``base`` keeps tokenizer + preprocessing."""
+
+    # The embed stage of the concept-DB build may hold preprocessed batches back until this many images are there: the
+    # towers' GEMMs reach their rate from a few thousand rows, and an embedding does not depend on its batch (bit for bit).
+    embed_accumulate = 256
+
+    def _read_towers(self, model, dev, ar):
+        visual = getattr(model, "visual", None)
+        if visual is not None and hasattr(visual, "attnpool") and hasattr(visual, "layer4"):
+            # CLIP ResNet (open_clip ModifiedResNet): conv trunk on PyTorch, attention pool + projection on the kernels;
+            # the text tower in open_clip's layout or synth's (`model.text.blocks`)
+            self.vision = NativeResNetVision(visual, dev)
+            text, found = _open_clip_text(model)
+            if found is not None:
+                self.text = NativeTextTower(text, device=dev, ar=ar, **found)
+            elif hasattr(getattr(model, "text", None), "blocks"):
+                self.text = NativeTextTower(model, model.text.blocks, dev, ar)
+            else:
+                raise TypeError("NativeClip: CLIP-ResNet image tower with a text tower that is neither open_clip's nor synth's layout")
+        elif visual is not None and hasattr(visual, "conv1") and hasattr(visual, "transformer"):
+            # open_clip CLIP: `visual` is the whole image tower
+            _require_clip_layout(model)
+            self.vision = NativeVisionTower(visual, visual.transformer.resblocks, dev, ar, pool=getattr(visual, "pool_type", "tok"),
+                                            ln_after_pool=getattr(visual, "final_ln_after_pool", False))
+            text, found = _open_clip_text(model)
+            if found is None:
+                # e.g. open_clip's CustomTextCLIP around a Hugging Face text encoder: `.text.transformer` is an HF model
+                raise TypeError(f"NativeClip reads open_clip's TextTransformer layout (`transformer.resblocks`); the text tower is "
+                                f"{type(text).__name__} around {type(getattr(text, 'transformer', None)).__name__} — run this model "
+                                "through its own torch modules (OpenClip without .native())")
+            self.text = NativeTextTower(text, device=dev, ar=ar, **found)
+        elif visual is not None and hasattr(model, "conv1") and hasattr(visual, "blocks"):
+            # synth._ClipModel: embedding members on the model, block stacks in .visual / .text
+            self.vision = NativeVisionTower(_SynthVisual(model), visual.blocks, dev, ar)
+            self.text = NativeTextTower(model, model.text.blocks, dev, ar)
+        else:
+            found = type(visual).__name__ if visual is not None else "no `visual` member"
+            raise TypeError(f"NativeClip reads open_clip's CLIP / VisionTransformer layout; {type(model).__name__} has {found} "
+                            "(timm trunks: NativeSigLip; convolutional / hybrid towers such as MobileCLIP are not built)")
+
+
 class _SynthVisual:
     """Adapter giving ``synth._ClipModel``'s image-tower members the names of open_clip's ``visual`` module."""
 
@@ -628,25 +701,23 @@ class _MapHead:
     """Weights of a MAP head (one learned probe attends over all tokens, out-projection, LayerNorm + MLP residual branch):
     transformers' ``SiglipMultiheadAttentionPoolingHead`` and timm's ``AttentionPoolLatent`` are the same computation."""
 
-    def __init__(self, probe, wq, bq, wkv, bkv, w_o, b_o, ln, w1, b1, w2, b2, heads: int, act: int):
+    def __init__(self, probe, q: _Layer, kv: _Layer, o: _Layer, ln, fc1: _Layer, fc2: _Layer, heads: int, act: int):
         W = probe.numel()
         self.heads, self.head_dim, self.act = int(heads), W // int(heads), act
         if self.head_dim not in _HEAD_DIMS or self.head_dim * self.heads != W:
             raise ValueError(f"MAP head: head_dim {self.head_dim} is not supported (built: {_HEAD_DIMS})")
         # the probe is the same for every image: its query projection is a constant of the model
-        self.q_probe = N.linear(probe.reshape(1, W).contiguous(), wq, bq).reshape(W).contiguous()
-        self.w_kv, self.b_kv = wkv, bkv  # (2W, W): rows [k | v]
-        self.w_o, self.b_o, self.ln, self.w1, self.b1, self.w2, self.b2 = w_o, b_o, ln, w1, b1, w2, b2
+        self.q_probe = N.linear(probe.reshape(1, W).contiguous(), q.w, q.b).reshape(W).contiguous()
+        self.kv, self.o, self.ln, self.fc1, self.fc2 = kv, o, ln, fc1, fc2  # kv: (2W, W), rows [k | v]
 
     @classmethod
     def from_transformers(cls, head: nn.Module, act: int, device):
         mha: nn.MultiheadAttention = head.attention
         W = mha.embed_dim
         ipw, ipb = _f32(mha.in_proj_weight, device), _f32(mha.in_proj_bias, device)
-        return cls(_f32(head.probe, device), ipw[:W].contiguous(), ipb[:W].contiguous(), ipw[W:].contiguous(), ipb[W:].contiguous(),
-                   _f32(mha.out_proj.weight, device), _bias(mha.out_proj, device), _ln(head.layernorm, device),
-                   _f32(head.mlp.fc1.weight, device), _bias(head.mlp.fc1, device), _f32(head.mlp.fc2.weight, device),
-                   _bias(head.mlp.fc2, device), mha.num_heads, act)
+        return cls(_f32(head.probe, device), _Layer(ipw[:W].contiguous(), ipb[:W].contiguous()),
+                   _Layer(ipw[W:].contiguous(), ipb[W:].contiguous()), _Layer.of(mha.out_proj, device), _ln(head.layernorm, device),
+                   _Layer.of(head.mlp.fc1, device), _Layer.of(head.mlp.fc2, device), mha.num_heads, act)
 
     @classmethod
     def from_timm(cls, pool: nn.Module, device):
@@ -657,10 +728,9 @@ class _MapHead:
             raise TypeError("timm AttentionPoolLatent with q/k normalisation is not built")
         if getattr(pool, "pool", "token") != "token":
             raise TypeError(f"timm AttentionPoolLatent pool={pool.pool!r}: only 'token'")
-        return cls(_f32(pool.latent, device), _f32(pool.q.weight, device), _bias(pool.q, device), _f32(pool.kv.weight, device),
-                   _bias(pool.kv, device), _f32(pool.proj.weight, device), _bias(pool.proj, device), _ln(pool.norm, device),
-                   _f32(pool.mlp.fc1.weight, device), _bias(pool.mlp.fc1, device), _f32(pool.mlp.fc2.weight, device),
-                   _bias(pool.mlp.fc2, device), pool.num_heads, _act_code(pool.mlp.act))
+        return cls(_f32(pool.latent, device), _Layer.of(pool.q, device), _Layer.of(pool.kv, device), _Layer.of(pool.proj, device),
+                   _ln(pool.norm, device), _Layer.of(pool.mlp.fc1, device), _Layer.of(pool.mlp.fc2, device), pool.num_heads,
+                   _act_code(pool.mlp.act))
 
 
 class NativeSigLipVision:
@@ -668,38 +738,34 @@ class NativeSigLipVision:
     then the MAP head (``sl_attention_pool``); the pooled token is the image feature, optionally followed by a Linear
     (open_clip ``TimmModel.head.proj``)."""
 
-    def __init__(self, conv: nn.Conv2d, pos: torch.Tensor, blocks: list, ln_post, head: _MapHead, device, split: bool,
+    def __init__(self, conv: nn.Conv2d, pos: torch.Tensor, blocks: list, ln_post, head: _MapHead, device, ar,
                  final_proj: nn.Linear | None = None):
         if conv.kernel_size != conv.stride:
             raise TypeError("NativeSigLip expects a patch embedding with stride == kernel size")
         self.patch = conv.kernel_size[0]
         self.width = conv.out_channels
-        self.w_patch = _f32(conv.weight.reshape(self.width, -1), device)
-        self.b_patch = _f32(conv.bias, device) if conv.bias is not None else None
+        self.patch_embed = _Layer(_f32(conv.weight.reshape(self.width, -1), device), _f32(conv.bias, device) if conv.bias is not None else None)
         self.pos = _f32(pos.reshape(-1, self.width), device)  # (n_patches, W)
-        self.split = split
-        if split:
-            self.s_patch = N.Split.of(self.w_patch)
-        self.tower = _Tower(blocks, split)
+        self.ar = ar
+        self.tower = _Tower(blocks, ar)
         self.ln_post = ln_post
         self.head = head
-        self.w_final = _f32(final_proj.weight, device) if final_proj is not None else None
-        self.b_final = _f32(final_proj.bias, device) if final_proj is not None and final_proj.bias is not None else None
-        if split:  # the head's GEMMs in the arithmetic of the blocks: its (B, W) products are small grids (gemm_skinny.hpp)
-            self.s_kv = N.Split.of(head.w_kv)
-            self.s_o, self.s_1, self.s_2 = N.Split.of(head.w_o), N.Split.of(head.w1), N.Split.of(head.w2)
-            self.s_final = N.Split.of(self.w_final) if self.w_final is not None else None
+        self.final = None
+        if final_proj is not None:
+            self.final = _Layer(_f32(final_proj.weight, device), _f32(final_proj.bias, device) if final_proj.bias is not None else None)
+        # the head's GEMMs in the arithmetic of the blocks: in split mode its (B, W) products are small grids (gemm_skinny.hpp)
+        ar.hold(self.patch_embed, head.kv, head.o, head.fc1, head.fc2, self.final)
 
     @classmethod
-    def from_transformers(cls, vm: nn.Module, cfg, device, split: bool):
+    def from_transformers(cls, vm: nn.Module, cfg, device, ar):
         """transformers ``SiglipVisionTransformer``: ``embeddings``, ``encoder.layers``, ``post_layernorm``, ``head``."""
         act = _act_code(getattr(cfg, "hidden_act", "gelu_pytorch_tanh"))
         blocks = [_read_hf_siglip_block(b, cfg.num_attention_heads, act, device) for b in vm.encoder.layers]
         return cls(vm.embeddings.patch_embedding, vm.embeddings.position_embedding.weight, blocks, _ln(vm.post_layernorm, device),
-                   _MapHead.from_transformers(vm.head, act, device), device, split)
+                   _MapHead.from_transformers(vm.head, act, device), device, ar)
 
     @classmethod
-    def from_open_clip_timm(cls, visual: nn.Module, device, split: bool):
+    def from_open_clip_timm(cls, visual: nn.Module, device, ar):
         """open_clip ``TimmModel``: ``trunk`` = timm ``VisionTransformer`` built with ``global_pool="map"``, ``head`` = the
         (possibly empty) projection ``nn.Sequential``."""
         t = visual.trunk
@@ -725,7 +791,7 @@ class NativeSigLipVision:
         if problems:
             raise TypeError("NativeSigLip does not implement this timm trunk: " + "; ".join(problems))
         blocks = [_read_timm_block(b, device) for b in t.blocks]
-        return cls(pe.proj, t.pos_embed, blocks, _ln(t.norm, device), _MapHead.from_timm(t.attn_pool, device), device, split, final)
+        return cls(pe.proj, t.pos_embed, blocks, _ln(t.norm, device), _MapHead.from_timm(t.attn_pool, device), device, ar, final)
 
     @torch.no_grad()
     def __call__(self, img: torch.Tensor) -> torch.Tensor:
@@ -738,46 +804,32 @@ class NativeSigLipVision:
         if T != self.pos.shape[0]:
             raise ValueError(f"image gives {T} patches, the positional embedding has {self.pos.shape[0]}")
         W = self.width
-        hd = self.head
+        ar, hd = self.ar, self.head
         x = torch.empty((B * T, W), dtype=torch.float32, device=img.device)
         # patch embedding GEMM (+ bias); its epilogue writes row (b, p) to token row b*T + p and adds pos[p]
-        if self.split:
-            patches = N.patchify(img, self.patch, out_split=N.Split(B * T, self.w_patch.shape[1], img.device))
-            N.linear3(patches, self.s_patch, self.b_patch, out=x, scatter=(T, T, 0), rowadd=self.pos)
-        else:
-            N.linear(N.patchify(img, self.patch), self.w_patch, self.b_patch, out=x, scatter=(T, T, 0), rowadd=self.pos)
+        ar.linear(ar.patchify(img, self.patch), self.patch_embed, out=x, scatter=(T, T, 0), rowadd=self.pos)
         x = self.tower.forward(x, B, T, causal=False)
-        if self.split:
-            h = N.layernorm(x, *self.ln_post, out_split=N.Split(B * T, W, img.device))
-            kv = N.linear3(h, self.s_kv, hd.b_kv)
-        else:
-            kv = N.linear(N.layernorm(x, *self.ln_post), hd.w_kv, hd.b_kv)
+        kv = ar.linear(ar.layernorm(x, self.ln_post), hd.kv)
         pooled = N.attention_pool(hd.q_probe, kv, B, T, hd.heads, hd.head_dim)  # (B, W)
-        if self.split:
-            dev = img.device
-            res = N.linear3(N.Split.of(pooled), self.s_o, hd.b_o)
-            hid = N.linear3(N.layernorm(res, *hd.ln, out_split=N.Split(B, W, dev)), self.s_1, hd.b1, act=hd.act,
-                            out_split=N.Split(B, hd.w1.shape[0], dev))
-            out = N.linear3(hid, self.s_2, hd.b2, residual=res, out=res)
-            return N.linear3(N.Split.of(out), self.s_final, self.b_final) if self.w_final is not None else out
-        res = N.linear(pooled, hd.w_o, hd.b_o)
-        hid = N.linear(N.layernorm(res, *hd.ln), hd.w1, hd.b1, act=hd.act)
-        out = N.linear(hid, hd.w2, hd.b2, residual=res, out=res)
-        return N.linear(out, self.w_final, self.b_final) if self.w_final is not None else out
+        res = ar.linear(ar.operand(pooled), hd.o)
+        hid = ar.linear(ar.layernorm(res, hd.ln), hd.fc1, act=hd.act, as_operand=True)
+        out = ar.linear(hid, hd.fc2, residual=res, out=res)
+        return _project(ar, out, self.final)
 
 
 class NativeSigLipText:
     """transformers ``SiglipTextTransformer``: token + position embeddings, NON-causal blocks (SigLIP pads to the context
     length and does not mask), ``final_layer_norm``, the LAST position pooled, then the ``head`` Linear (with bias)."""
 
-    def __init__(self, tm: nn.Module, cfg, device, split: bool):
+    def __init__(self, tm: nn.Module, cfg, device, ar):
         self.table = _f32(tm.embeddings.token_embedding.weight, device)
         self.pos = _f32(tm.embeddings.position_embedding.weight, device)
         act = _act_code(getattr(cfg, "hidden_act", ""))
-        self.tower = _Tower([_read_hf_siglip_block(b, cfg.num_attention_heads, act, device) for b in tm.encoder.layers], split)
+        self.tower = _Tower([_read_hf_siglip_block(b, cfg.num_attention_heads, act, device) for b in tm.encoder.layers], ar)
         self.ln_final = _ln(tm.final_layer_norm, device)
-        self.w_head, self.b_head = _f32(tm.head.weight, device), _f32(tm.head.bias, device)
-        self.s_head = N.Split.of(self.w_head) if split else None
+        self.head = _Layer(_f32(tm.head.weight, device), _f32(tm.head.bias, device))
+        self.ar = ar
+        ar.hold(self.head)
 
     @torch.no_grad()
     def __call__(self, tokens: torch.Tensor) -> torch.Tensor:
@@ -788,7 +840,7 @@ class NativeSigLipText:
         x = N.embed_tokens(self.table, tokens, self.pos[:T].contiguous())
         rows = torch.arange(B, device=tokens.device, dtype=torch.int64) * T + (T - 1)
         picked = self.tower.forward(x, B, T, causal=False, pool_rows=rows)
-        return _project(N.layernorm(picked, *self.ln_final), self.w_head, self.b_head, self.s_head)
+        return _project(self.ar, N.layernorm(picked, *self.ln_final), self.head)
 
 
 def friendly_batch(tokens: int, width: int, mlp: int, device=None, lo: int = 64, hi: int = 256) -> int:
@@ -813,7 +865,7 @@ def friendly_batch(tokens: int, width: int, mlp: int, device=None, lo: int = 64,
     return best
 
 
-class NativeSigLip(AbstractVLM):
+class NativeSigLip(_NativeVLM):
     """``AbstractVLM`` running the towers of a SigLIP-layout model on HIP kernels.
 
     ``base.model`` is either what the reference's ``SigLipV2`` constructs (foundation_models/clip.py:190-211: open_clip's
@@ -822,71 +874,25 @@ class NativeSigLip(AbstractVLM):
     (``vision_model`` / ``text_model``; the geometry of SigLIP-so400m — width 1152, head_dim 72 — is what BASELINE
     configs[3] names).  Tokenizer and host preprocessing stay ``base``'s; ``preprocess`` as for :class:`NativeClip`."""
 
-    embed_accumulate = 64  # see NativeClip; replaced per instance in __init__ (tile-friendly row count for the tower's geometry)
+    embed_accumulate = 64  # see NativeClip; replaced per instance in _read_towers (tile-friendly row count for the tower's geometry)
 
-    def __init__(self, base, device=None, gemm: str = "bf16x3", preprocess=None):
-        if gemm not in ("bf16x3", "f32"):
-            raise ValueError("gemm must be 'bf16x3' or 'f32'")
-        model = base.model
+    def _read_towers(self, model, dev, ar):
         hf = hasattr(model, "vision_model") and hasattr(model, "text_model") and hasattr(model.vision_model, "head")
         oc = hasattr(model, "visual") and hasattr(model.visual, "trunk") and hasattr(model, "text") and hasattr(model.text, "transformer")
-        if not (hf or oc):
+        text, found = _open_clip_text(model) if oc else (None, None)
+        if not (hf or found is not None):
             raise TypeError("NativeSigLip expects transformers' SiglipModel layout (`vision_model` with a MAP `head`, `text_model`) "
                             "or open_clip's CustomTextCLIP layout (`visual.trunk` = timm ViT, `text` = TextTransformer)")
-        dev = torch.device(device) if device is not None else next(model.parameters()).device
-        if dev.type != "cuda":
-            dev = N.default_device()
-        self._device = dev
-        self.base = base
-        base.to(dev)
-        split = gemm == "bf16x3"
         if hf:
-            self.vision = NativeSigLipVision.from_transformers(model.vision_model, model.config.vision_config, dev, split)
-            self.text = NativeSigLipText(model.text_model, model.config.text_config, dev, split)
+            self.vision = NativeSigLipVision.from_transformers(model.vision_model, model.config.vision_config, dev, ar)
+            self.text = NativeSigLipText(model.text_model, model.config.text_config, dev, ar)
         else:
-            self.vision = NativeSigLipVision.from_open_clip_timm(model.visual, dev, split)
-            text = model.text
-            self.text = NativeTextTower(text, text.transformer.resblocks, dev, split, pool=getattr(text, "pool_type", "argmax"),
-                                        causal=getattr(text, "attn_mask", None) is not None)
-        self.name = f"native-{gemm}-" + getattr(base, "name", type(base).__name__)
-        self.embed_accumulate = friendly_batch(self.vision.pos.shape[0], self.vision.width, self.vision.tower.blocks[0].w_fc.shape[0], dev)
-        if preprocess == "device":
-            from semanticlens_amd.foundation_models.preprocess import DevicePreprocess
-
-            preprocess = DevicePreprocess.from_transform(base.preprocessor)
-        self._preprocess = preprocess.to(dev) if preprocess is not None else None
-
-    @property
-    def device(self):
-        return self._device
-
-    @property
-    def device_preprocess(self):
-        """The ``DevicePreprocess`` behind :meth:`preprocess`, or None when ``base``'s host transform runs."""
-        return self._preprocess
-
-    def to(self, device):
-        if torch.device(device).type != "cuda":
-            raise N.NativeLibraryError("NativeSigLip runs on a HIP device only")
-        return self
-
-    def encode_image(self, img):
-        return self.vision(img)
-
-    def encode_text(self, tokens):
-        return self.text(tokens)
-
-    def preprocess(self, img):
-        if self._preprocess is not None:
-            out = self._preprocess(img)
-            return out.unsqueeze(0) if out.ndim == 3 else out
-        return self.base.preprocess(img)
-
-    def tokenize(self, txt, *args, **kwargs):
-        return self.base.tokenize(txt, *args, **kwargs)
+            self.vision = NativeSigLipVision.from_open_clip_timm(model.visual, dev, ar)
+            self.text = NativeTextTower(text, device=dev, ar=ar, **found)
+        self.embed_accumulate = friendly_batch(self.vision.pos.shape[0], self.vision.width, self.vision.tower.blocks[0].fc.w.shape[0], dev)
 
 
-class NativeTextClip(AbstractVLM):
+class NativeTextClip(_NativeVLM):
     """The wrapped model with its TEXT tower on the kernels and its image tower left to PyTorch — for CLIP models whose image
     tower the native classes do not read: MobileCLIP (``ClipMobile``, foundation_models/clip.py:214-247 — the reference
     tutorial's foundation model: a FastViT hybrid of re-parameterised convolutions behind open_clip's ``TimmModel``) and any
@@ -895,59 +901,19 @@ class NativeTextClip(AbstractVLM):
     ``encode_image`` is ``base``'s own (the embed stage treats it like any user ``AbstractVLM``).  ``preprocess`` as for
     :class:`NativeClip`."""
 
-    def __init__(self, base, device=None, gemm: str = "bf16x3", preprocess=None):
-        if gemm not in ("bf16x3", "f32"):
-            raise ValueError("gemm must be 'bf16x3' or 'f32'")
-        model = base.model
-        dev = torch.device(device) if device is not None else next(model.parameters()).device
-        if dev.type != "cuda":
-            dev = N.default_device()
-        self._device, self.base = dev, base
-        base.to(dev)
-        text = model.text if hasattr(getattr(model, "text", None), "transformer") else model
-        if not hasattr(getattr(text, "transformer", None), "resblocks") or not hasattr(text, "token_embedding"):
+    _name = "native-text-"
+
+    def _read_towers(self, model, dev, ar):
+        text, found = _open_clip_text(model)
+        if found is None or not hasattr(text, "token_embedding"):
             raise TypeError(f"NativeTextClip reads open_clip's TextTransformer layout (`token_embedding`, `transformer.resblocks`, "
                             f"`ln_final`, `text_projection`); found {type(text).__name__}")
-        pool = getattr(text, "pool_type", None) or getattr(model, "text_pool_type", "argmax")
-        if pool not in ("argmax", "first", "last"):
-            raise TypeError(f"text pool_type={pool!r} (only 'argmax', 'first', 'last')")
-        self.text = NativeTextTower(text, text.transformer.resblocks, dev, gemm == "bf16x3", pool=pool,
-                                    causal=getattr(text, "attn_mask", None) is not None)
-        self.name = f"native-text-{gemm}-" + getattr(base, "name", type(base).__name__)
-        if preprocess == "device":
-            from semanticlens_amd.foundation_models.preprocess import DevicePreprocess
-
-            preprocess = DevicePreprocess.from_transform(base.preprocessor)
-        self._preprocess = preprocess.to(dev) if preprocess is not None else None
-
-    @property
-    def device(self):
-        return self._device
-
-    @property
-    def device_preprocess(self):
-        """The ``DevicePreprocess`` behind :meth:`preprocess`, or None when ``base``'s host transform runs."""
-        return self._preprocess
-
-    def to(self, device):
-        if torch.device(device).type != "cuda":
-            raise N.NativeLibraryError("NativeTextClip runs on a HIP device only")
-        return self
+        if found["pool"] not in ("argmax", "first", "last"):
+            raise TypeError(f"text pool_type={found['pool']!r} (only 'argmax', 'first', 'last')")
+        self.text = NativeTextTower(text, device=dev, ar=ar, **found)
 
     def encode_image(self, img):
         return self.base.encode_image(img)
-
-    def encode_text(self, tokens):
-        return self.text(tokens)
-
-    def preprocess(self, img):
-        if self._preprocess is not None:
-            out = self._preprocess(img)
-            return out.unsqueeze(0) if out.ndim == 3 else out
-        return self.base.preprocess(img)
-
-    def tokenize(self, txt, *args, **kwargs):
-        return self.base.tokenize(txt, *args, **kwargs)
 
 
 def native_model(base, gemm: str = "bf16x3", preprocess=None, image_tower: str = "native"):

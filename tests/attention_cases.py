@@ -1,6 +1,6 @@
 """Attention inputs whose softmax is NOT that of `torch.randn`: one head's q, k, v for a named logit pattern, their float64
 reference, a derived per-element error bound, and a host restatement of the two kernels' arithmetic
-(`attention_mfma_kernel<D>` and `attention_bf16x3_kernel<D, MAXW>`, semanticlens_amd/csrc/encoder.hip).  A helper, not a test:
+(`attention_mfma_kernel<D>` and `attention_bf16x3_kernel<D, MAXW>`, semanticlens_amd/csrc/encoder_attention.hip).  A helper, not a test:
 tests/test_attention_bound_host.py holds every case to its description and the emulation to half the bound without a GPU,
 tests/test_gpu_attention_values.py runs the kernels on the same inputs, docs/ATTENTION_VALUES.md is the table.
 
@@ -134,7 +134,7 @@ _LN2 = torch.tensor(6.93147182e-01, dtype=torch.float32)
 
 
 def exp_neg(x: torch.Tensor) -> torch.Tensor:
-    """`exp_neg` of encoder.hip on fp32 `x`: the clamp at -104, 2^(x log2 e) with the product's rounding error and the low part
+    """`exp_neg` of encoder_attention.hip on fp32 `x`: the clamp at -104, 2^(x log2 e) with the product's rounding error and the low part
     of the constant folded back in.  The fused multiply-adds are taken in float64 and rounded once; the hardware exp2 is the
     float64 one rounded to fp32, with results below 2^-126 flushed to 0 as the instruction does."""
     x = x.clamp_min(-104.0)

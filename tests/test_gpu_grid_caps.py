@@ -168,7 +168,7 @@ def patches(img: torch.Tensor, P: int) -> torch.Tensor:
 
 @pytest.mark.parametrize("P,Hi,Wi", [(4, 8, 12), (2, 4, 6)])
 def test_patchify_past_its_grid(P, Hi, Wi):
-    """`patchify_kernel` (P = 4: items are float4) and `patchify_scalar_kernel` (P = 2: floats), encoder.hip:823 `grid_for`:
+    """`patchify_kernel` (P = 4: items are float4) and `patchify_scalar_kernel` (P = 2: floats), encoder.hip:206 `grid_for`:
     fp32 output and the split-bf16 output, bit for bit against reshape / permute."""
     C, cap = 3, cap_grid_for()
     per_image = C * Hi * Wi // (4 if P % 4 == 0 else 1)

@@ -208,7 +208,7 @@ def torch_fp32_error(name: str) -> float:
 
 
 def activation_bound(name: str, z64: torch.Tensor) -> torch.Tensor:
-    """Pointwise absolute bound at (finite) float64 arguments `z64`.  GELU on [-8, 8]: the kernel's own claim (encoder.hip,
+    """Pointwise absolute bound at (finite) float64 arguments `z64`.  GELU on [-8, 8]: the kernel's own claim (encoder_epilogue.hpp,
     `erf_as`), 4.7e-7, and one fp32 rounding of the result.  Elsewhere: four times torch's own fp32 distance from float64 on the
     grid (the kernels have two 1-ulp approximate instructions and two roundings that torch's op has not), never below
     2^-22 max(1, |want|)."""

@@ -661,16 +661,24 @@ def test_pinned_stack_falls_back_to_default_collate_without_a_device():
 
 
 def test_native_block_refuses_head_dims_the_attention_kernels_are_not_built_for():
-    """`_HEAD_DIMS` listed every multiple of 8 while encoder.hip instantiates eight of them; a head_dim-48 model
-    constructed, split all its weights and died on the first encode.  Now refused at construction."""
+    """`_HEAD_DIMS` listed every multiple of 8 while the attention kernels are instantiated for eight of them; a
+    head_dim-48 model constructed, split all its weights and died on the first encode.  Now refused at construction.
+    encoder_attention.hip states the built list once (`SL_ATTENTION_HEAD_DIMS`); both entry points reach their kernels through
+    `attention_dispatch` over exactly that list, and nothing else in the unit selects a kernel by head_dim."""
     import re
 
     from semanticlens_amd.foundation_models import native_clip as nc
 
-    src = (ROOT / "semanticlens_amd" / "csrc" / "encoder.hip").read_text()
-    for fn in ("launch_attention_mfma", "launch_attention_bf16x3"):
-        built = sorted({int(m) for m in re.findall(r"case (\d+): return %s<\1>" % fn, src)})
-        assert tuple(built) == nc._HEAD_DIMS, (fn, built)
+    src = (ROOT / "semanticlens_amd" / "csrc" / "encoder_attention.hip").read_text()
+    lists = re.findall(r"^#define SL_ATTENTION_HEAD_DIMS (.+)$", src, re.M)
+    assert len(lists) == 1 and tuple(int(d) for d in lists[0].split(",")) == nc._HEAD_DIMS, lists
+    for fn, kernel in (("sl_attention", "attention_mfma_kernel<D>"), ("sl_attention_bf16x3", "attention_bf16x3_kernel<D, 8>")):
+        body = re.search(r"^SL_API int %s\(.*?^}" % fn, src, re.M | re.S).group(0)
+        assert kernel in body, (fn, kernel)
+        assert len(re.findall(r'return attention_dispatch\("%s",' % fn, body)) == 1, fn
+        assert "std::integer_sequence<int, SL_ATTENTION_HEAD_DIMS>{}" in body, fn
+    assert not re.search(r"\bcase \d+:|head_dim ==\s*\d", src) and src.count("SL_ATTENTION_HEAD_DIMS") == 4  # define, message, two entry points
+    assert len(re.findall(r"\battention_(?:mfma|bf16x3)_kernel<", src)) == 4  # each kernel is named in its own entry point only
     for width, heads in ((192, 4), (320, 8), (448, 8), (896, 8), (960, 8)):  # head_dim 48, 40, 56, 112, 120
         with pytest.raises(ValueError, match="head_dim"):
             nc._BlockWeights(width, heads, 0)

@@ -1,6 +1,6 @@
 // LAB ONLY — not part of libsemanticlens_hip.so.  The tower's first attention kernel (round 1: VALU, four lanes per query row,
-// head_dim 64, T <= 256), superseded by attention_mfma_kernel / attention_bf16x3_kernel (encoder.hip) and retired in round 6.
-// Kept as source for A/B history; include it after encoder.hip's helpers (bits_f32, f32_bits, store_split, split_kp) to build it.
+// head_dim 64, T <= 256), superseded by attention_mfma_kernel / attention_bf16x3_kernel (encoder_attention.hip) and retired in round 6.
+// Kept as source for A/B history; include it after encoder_attention.hip's includes (common.hpp: bits_f32, f32_bits; gemm_bf16x3.hpp: store_split, split_kp) to build it.
 #pragma once
 
 // ---- multi-head attention, head_dim 64 --------------------------------------------------------------------
