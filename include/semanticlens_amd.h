@@ -507,6 +507,31 @@ int sl_batchnorm_infer_relu_maxpool(const float* d_x, int64_t B, int64_t C, int6
                                     const float* d_var, const float* d_scale, const float* d_bias, double eps, int kh, int kw,
                                     int sh, int sw, int ph, int pw, float* d_y, void* stream);
 
+/* ---- K27: a 64 -> 256 channel 1x1 convolution inside the residual tail ----------------
+ * d_x (N,64,HW), d_y and d_identity (N,256,HW): contiguous NCHW fp32, 16-byte aligned, distinct buffers; d_w (256,64) fp32,
+ * the Conv2d's weight (no bias).  N*256*HW < 2^31; HW need not be a multiple of anything.  The product is accumulated by
+ * v_mfma_f32_16x16x4_f32 in ascending k in `split`'s partial chains, added at the end:
+ *   0 one chain; 1 two chains over k [0,32) [32,64); 2 two chains, the 16 steps of four k dealt alternately;
+ *   3 four chains over runs of 16 k, added in order; 4 the same, added pairwise; 5 / 6 four chains dealt round-robin, in
+ *   order / pairwise.
+ * Split 0 reproduced MIOpen's GemmFwd1x1_0_1 bit for bit at (256, 64, 56, 56) (profiles/k27_step0_probe.txt); the others
+ * exist for tools/conv_tail_probe.py.  What the GEMM library runs depends on its choice for the shape, so a caller still proves
+ * a site on its own input before it trusts it (component_visualization/_bn_fuse.py).
+ * sl_conv1x1_64_256 writes the raw product; d_korder, when given, is 64 int32: the input channel that MFMA step s takes in
+ * its k slot g is d_korder[4 s + g] (a permutation of 0..63; NULL is ascending).  The other two take split 0 and apply the
+ * K16 / K19 tails to the product(s) before anything is stored: clamp_min(bn(W x) + identity, 0) and clamp_min(bn_a(Wa xa) + bn_b(Wb xb), 0), the
+ * BatchNorm value rounded to fp32 before the add and bn_a's the left operand.  W and the per-channel tensors are read on
+ * every launch. */
+int sl_conv1x1_64_256(const float* d_x, const float* d_w, int64_t N, int64_t HW, int split, const int32_t* d_korder, float* d_y,
+                      void* stream);
+int sl_conv1x1_bn_add_relu(const float* d_x, const float* d_w, const float* d_mean, const float* d_var, const float* d_scale,
+                           const float* d_bias, double eps, const float* d_identity, int64_t N, int64_t HW, float* d_y,
+                           void* stream);
+int sl_conv1x1_bn_add_conv1x1_bn_relu(const float* d_xa, const float* d_wa, const float* d_mean_a, const float* d_var_a,
+                                      const float* d_scale_a, const float* d_bias_a, double eps_a, const float* d_xb,
+                                      const float* d_wb, const float* d_mean_b, const float* d_var_b, const float* d_scale_b,
+                                      const float* d_bias_b, double eps_b, int64_t N, int64_t HW, float* d_y, void* stream);
+
 /* ---- K17: streaming fp32 row top-k — the selection behind label_components / search_components --------
  * No reference counterpart.  State = d_vals (R,k) fp32 + d_ids (R,k) int64, sorted best-first per row; sl_topk_init writes
  * the empty slots (value -inf, id -1).  Order: NaN first, then the larger value, -0.0 == +0.0, equal keys by the smaller id; a

@@ -127,6 +127,10 @@ SIGNATURES = {
                                               _i64, _vp, _vp]),
     "sl_batchnorm_infer_relu_maxpool": (_int, [_vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, ctypes.c_double, _int, _int, _int,
                                                _int, _int, _int, _vp, _vp]),
+    "sl_conv1x1_64_256": (_int, [_vp, _vp, _i64, _i64, _int, _vp, _vp, _vp]),
+    "sl_conv1x1_bn_add_relu": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_double, _vp, _i64, _i64, _vp, _vp]),
+    "sl_conv1x1_bn_add_conv1x1_bn_relu": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_double, _vp, _vp, _vp, _vp, _vp, _vp,
+                                                 ctypes.c_double, _i64, _i64, _vp, _vp]),
     "sl_topk_init": (_int, [_vp, _vp, _i64, _i64, _vp]),
     "sl_topk_merge": (_int, [_vp, _vp, _i64, _i64, _vp, _i64, _i64, _i64, _vp, _sz, _vp]),
     "sl_topk_merge_ws_bytes": (_sz, [_i64, _i64, _i64]),
@@ -1616,6 +1620,86 @@ def batchnorm_infer_relu_maxpool(x: torch.Tensor, mean: torch.Tensor, var: torch
         rc = lib().sl_batchnorm_infer_relu_maxpool(_ptr(x), B, C, H, W, _ptr(mean), _ptr(var), _ptr(weight), _ptr(bias),
                                                    float(eps), kh, kw, sh, sw, ph, pw, _ptr(out), _stream(x))
     _check(rc, "sl_batchnorm_infer_relu_maxpool")
+    return out
+
+
+# ------------------------------------------------------------------------------------------------
+# K27
+# ------------------------------------------------------------------------------------------------
+CONV_TAIL_IN, CONV_TAIL_OUT = 64, 256  # the one pointwise shape the kernels take
+CONV_TAIL_SPLITS = 7  # candidates for how the GEMM behind a 1x1 convolution cuts K = 64 into partial sums (semanticlens_amd.h)
+CONV_TAIL_MAX_ELEMENTS = (1 << 31) - 1  # of the output
+
+
+def _conv_tail_operands(what: str, x: torch.Tensor, w: torch.Tensor):
+    if x.dim() != 4 or x.shape[1] != CONV_TAIL_IN or w.numel() != CONV_TAIL_IN * CONV_TAIL_OUT or w.shape[:2] != (CONV_TAIL_OUT,
+                                                                                                                 CONV_TAIL_IN):
+        raise ValueError(f"{what}: a (N, {CONV_TAIL_IN}, H, W) input and a ({CONV_TAIL_OUT}, {CONV_TAIL_IN}[, 1, 1]) weight expected, "
+                         f"got {tuple(x.shape)} and {tuple(w.shape)}")
+    for t in (x, w):
+        if t.dtype is not torch.float32 or not t.is_cuda or t.device != x.device or not t.is_contiguous() or t.data_ptr() % 16:
+            raise ValueError(f"{what}: operands must be contiguous fp32 on one HIP device, 16-byte aligned")
+    B, _, H, W = x.shape
+    return B, H, W
+
+
+def _conv_tail_out(x: torch.Tensor) -> torch.Tensor:
+    return torch.empty((x.shape[0], CONV_TAIL_OUT, x.shape[2], x.shape[3]), dtype=x.dtype, device=x.device)
+
+
+def _conv_tail_bn(what: str, x: torch.Tensor, bn):
+    for p in bn[:4]:
+        if p.dtype is not torch.float32 or p.device != x.device or not p.is_contiguous() or p.numel() != CONV_TAIL_OUT:
+            raise ValueError(f"{what}: per-channel tensors must be contiguous fp32 of {CONV_TAIL_OUT} elements on {x.device}")
+
+
+def conv1x1_64_256(x: torch.Tensor, w: torch.Tensor, split: int, k_order: torch.Tensor | None = None) -> torch.Tensor:
+    """The raw product of a 64 -> 256 channel pointwise convolution (no bias) under partial-sum candidate ``split``; ``k_order``
+    (64 int32 on the device) is the order in which the MFMA steps take the input channels, ascending when None."""
+    B, H, W = _conv_tail_operands("conv1x1_64_256", x, w)
+    out = _conv_tail_out(x)
+    if k_order is not None and (k_order.dtype is not torch.int32 or k_order.device != x.device or k_order.numel() != CONV_TAIL_IN
+                                or not k_order.is_contiguous()
+                                or sorted(k_order.tolist()) != list(range(CONV_TAIL_IN))):
+        raise ValueError("conv1x1_64_256: k_order must be a permutation of 0..63 as contiguous int32 on the input's device")
+    with _on(x.device):
+        rc = lib().sl_conv1x1_64_256(_ptr(x), _ptr(w), B, H * W, int(split), _ptr(k_order), _ptr(out), _stream(x))
+    _check(rc, "sl_conv1x1_64_256")
+    return out
+
+
+def conv1x1_bn_add_relu(x: torch.Tensor, w: torch.Tensor, bn, identity: torch.Tensor) -> torch.Tensor:
+    """``relu_(F.batch_norm(F.conv2d(x, w), *bn) + identity)`` in one pass; ``bn`` is ``(mean, var, weight, bias, eps)``."""
+    B, H, W = _conv_tail_operands("conv1x1_bn_add_relu", x, w)
+    out = _conv_tail_out(x)
+    _conv_tail_bn("conv1x1_bn_add_relu", x, bn)
+    if (identity.shape != out.shape or identity.dtype is not torch.float32 or identity.device != x.device
+            or not identity.is_contiguous() or identity.data_ptr() % 16):
+        raise ValueError(f"conv1x1_bn_add_relu: the identity must be contiguous fp32 of shape {tuple(out.shape)} on {x.device}")
+    with _on(x.device):
+        rc = lib().sl_conv1x1_bn_add_relu(_ptr(x), _ptr(w), *(_ptr(p) for p in bn[:4]), float(bn[4]), _ptr(identity), B, H * W,
+                                          _ptr(out), _stream(x))
+    _check(rc, "sl_conv1x1_bn_add_relu")
+    return out
+
+
+def conv1x1_bn_add_conv1x1_bn_relu(xa: torch.Tensor, wa: torch.Tensor, bn_a, xb: torch.Tensor, wb: torch.Tensor,
+                                   bn_b) -> torch.Tensor:
+    """``relu_(F.batch_norm(F.conv2d(xa, wa), *bn_a) + F.batch_norm(F.conv2d(xb, wb), *bn_b))`` in one pass; ``xa``'s side is the
+    left operand of the add, as in ``batchnorm_infer_add_bn_relu``."""
+    what = "conv1x1_bn_add_conv1x1_bn_relu"
+    B, H, W = _conv_tail_operands(what, xa, wa)
+    _conv_tail_operands(what, xb, wb)
+    if xb.shape != xa.shape or xb.device != xa.device:
+        raise ValueError(f"{what}: two inputs of one shape and device expected, got {tuple(xa.shape)} and {tuple(xb.shape)}")
+    _conv_tail_bn(what, xa, bn_a)
+    _conv_tail_bn(what, xa, bn_b)
+    out = _conv_tail_out(xa)
+    with _on(xa.device):
+        rc = lib().sl_conv1x1_bn_add_conv1x1_bn_relu(_ptr(xa), _ptr(wa), *(_ptr(p) for p in bn_a[:4]), float(bn_a[4]), _ptr(xb),
+                                                     _ptr(wb), *(_ptr(p) for p in bn_b[:4]), float(bn_b[4]), B, H * W,
+                                                     _ptr(out), _stream(xa))
+    _check(rc, what)
     return out
 
 

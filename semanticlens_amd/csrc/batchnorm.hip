@@ -21,14 +21,11 @@
 // SL_PROF_BATCHNORM counts BatchNorm2d evaluations, so a call of EPI_ADD_BN_RELU leaves two records in the slot: the kernel's
 // (its time, 3 x total x 4 bytes) and an empty one (work 0, its two events recorded back to back on the stream).  The slot's
 // time and bytes are the kernels'; its time over its count is not a per-launch average.
-#include "common.hpp"
+#include "bn_apply.hpp"
 
 namespace sl {
 namespace {
 
-typedef float f4 __attribute__((ext_vector_type(4)));
-
-enum { EPI_PLAIN = 0, EPI_RELU = 1, EPI_ADD_RELU = 2, EPI_ADD_BN_RELU = 3 };
 enum { POL_PLAIN = 0, POL_NT_STORE = 1, POL_NT_BOTH = 2 };
 
 constexpr int kBlock = 256;
@@ -39,44 +36,7 @@ constexpr int64_t kLdsPerCu = 160 * 1024;
 constexpr size_t kDualResidentFrom = 32 * 1024;  // EPI_ADD_BN_RELU: above this many bytes of tables the grid is the resident blocks
 constexpr int64_t kMaxTotal = (int64_t)1 << 31;
 
-// MIOpen's form: the estimate is added in fp32 and the root is the hardware's v_rsq_f32 (not a divide by a square root, not the
-// double-precision route: DESIGN.md K16 counts what each of those misses).
-__device__ inline float bn_inv_std(float var, double eps) { return __builtin_amdgcn_rsqf(fabsf(var + (float)eps)); }
-
-// k = {mean, inv_std, scale, bias}
-__device__ inline float bn_value(float x, const f4 k) {
-  const float xhat = (x - k.x) * k.y;
-  return __fmaf_rn(k.z, xhat, k.w);  // one rounding: a separate multiply and add differs in a quarter of the elements
-}
-
-// ATen's clamp_min functor: NaN passes through with its bits, max(-0.0, 0) is +0.0
-__device__ inline float relu_clamp(float v) { return v != v ? v : fmaxf(v, 0.f); }
-
-// a + b as ATen's add kernel computes it.  Only two NaN operands tell the forms apart: the hardware returns one operand's payload,
-// which one depends on the instruction and on the operand's position, and the compiler is free to commute an add or to pair
-// two of them into a packed one (it did: v_pk_add_f32 kept the other payload in every such element, whichever tensor was the
-// left operand).  So the instruction is written out, with the right-hand operand first: the form that matched on the device.
-__device__ inline float add_as_aten(float a, float b) {
-  float r;
-  asm("v_add_f32_e32 %0, %1, %2" : "=v"(r) : "v"(b), "v"(a));
-  return r;
-}
-
-// One BatchNorm2d's per-channel tensors, as the module holds them.
-struct BnParams {
-  const float *mean, *var, *scale, *bias;
-  double eps;
-};
-
-// r is the residual (EPI_ADD_RELU) or the second tensor's element, kb its constants (EPI_ADD_BN_RELU)
-template <int EPI>
-__device__ inline float bn_finish(float x, const f4 k, float r, const f4 kb) {
-  float y = bn_value(x, k);
-  if constexpr (EPI == EPI_ADD_RELU) y = y + r;  // y is an fp32 value here, as when it went through memory
-  if constexpr (EPI == EPI_ADD_BN_RELU) y = add_as_aten(y, bn_value(r, kb));  // two fp32 values; x's is the left operand, as in the model
-  if constexpr (EPI != EPI_PLAIN) y = relu_clamp(y);
-  return y;
-}
+// bn_inv_std, bn_value, relu_clamp, add_as_aten, BnParams and bn_finish: bn_apply.hpp (conv_tail.hip applies them too)
 
 template <int POL>
 __device__ inline f4 ld4(const f4* p) {
@@ -115,8 +75,8 @@ __global__ __launch_bounds__(kBlock) void batchnorm_kernel(const float* __restri
   constexpr bool DUAL = EPI == EPI_ADD_BN_RELU;
   extern __shared__ f4 tab[];
   for (uint32_t c = threadIdx.x; c < C; c += kBlock) {
-    tab[c] = f4{a.mean[c], bn_inv_std(a.var[c], a.eps), a.scale[c], a.bias[c]};
-    if constexpr (DUAL) tab[C + c] = f4{b.mean[c], bn_inv_std(b.var[c], b.eps), b.scale[c], b.bias[c]};
+    tab[c] = bn_constants(a, c);
+    if constexpr (DUAL) tab[C + c] = bn_constants(b, c);
   }
   __syncthreads();
   const uint32_t second = DUAL ? C : 0u;  // tab[second + c]: the second tensor's constants (unused otherwise)
