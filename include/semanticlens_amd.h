@@ -642,6 +642,47 @@ int sl_rank_merge(int64_t* d_counts, int64_t R, int64_t T, const float* d_cand, 
                   const float* d_key_vals, const int64_t* d_key_ids, void* stream);
 int64_t sl_rank_merge_splits(int64_t R, int64_t B); /* waves per row the launch uses; 1 for most shapes */
 
+/* ---- K28: the step of an orthogonal matching pursuit over a vocabulary — behind decompose_components ----------
+ * No reference counterpart.  Per component x (a row of d_x (C,D) fp32) the pursuit looks for a few rows of d_w (V,D) fp32 whose
+ * normalised forms span x / |x|.  A pass over the vocabulary is sl_cosine_nt + sl_topk_merge of the current residuals with k = t + 1
+ * (one of t + 1 candidates is not among the t chosen); sl_omp_step then does, in ONE launch, what torch does per step with a gather
+ * of (C,t+1,D) rows, a batched Gram product, cholesky, cholesky_solve, a bmm and a subtraction.  Norms, cosines, the factor, the
+ * weights and the residual are float64 from the fp32 inputs; the rules are csrc/omp_state.hpp's, host-checkable.
+ *
+ * State per component, s = the number of terms asked for, 1 <= s <= SL_OMP_MAX_TERMS:
+ *   d_ids (C,s) int64        chosen row of d_w per term, in the order chosen; -1 unused
+ *   d_chol (C,s(s+1)/2) f64  Cholesky factor of the chosen unit rows' Gram matrix, lower triangle packed row by row
+ *   d_rhs (C,s) f64          their dot products with x / |x|
+ *   d_coefs (C,s) f64        the least-squares weights after the last accepted term; 0 unused
+ *   d_corr (C,s) fp32        the candidate value a term was chosen with; NaN unused
+ *   d_explained (C,s) f64    1 - |residual|^2 after each term; an unused slot repeats the last value (0 without a term)
+ *   d_n_terms (C,) int32     terms accepted
+ *   d_finished (C,) int32    1 once the component has stopped; later steps leave all of its state alone
+ *   d_residual (C,D) fp32    the WORKING residual the next pass reads: x / |x| - sum a_i w_i / |w_i|, zeros once finished
+ *   d_last (C,D) fp32        the residual to report: written when a component stops and by step s - 1; complete after step s - 1
+ * sl_omp_init writes x / |x| into d_residual and the empty state (d_chol and d_rhs need no clearing).  A component that is a zero
+ * row or has a non-finite coordinate is finished at once: d_explained and its d_last row NaN, d_residual zeros.
+ *
+ * sl_omp_step, step t in [0, s), called for t = 0, 1, .., s - 1 in turn.  Candidates: d_cand_vals / d_cand_ids (C,k_cand), k_cand >= t + 1,
+ * best first in K17's order, as sl_topk_merge leaves them.  Per unfinished component: take the first candidate whose id lies in
+ * [0, V) and is not among the t chosen (any other id is an empty slot and is never used as an index).  The component stops
+ * (d_n_terms = t) when there is none, when its value is NaN or <= min_correlation, or when appending its row gives a Cholesky pivot
+ * 1 - z.z below SL_OMP_MIN_PIVOT (the row depends linearly on the chosen ones; a row of zero or non-finite norm stops here too).
+ * Otherwise the row is appended, the weights solved, the residual recomputed from x — never updated from the previous one — and
+ * d_explained[t] written; the component also stops when |residual|^2 <= SL_OMP_RESIDUAL_DONE.  Both constants are design choices.
+ * min_correlation in [0, 1).  Rows are read 16 bytes per lane when D % 4 == 0 and d_x, d_w, d_residual, d_last are 16-byte
+ * aligned, else 4 bytes per lane; any 4-byte aligned bases work.  No floating-point atomics: the same inputs give the same bits.
+ * C == 0 is a no-op. */
+#define SL_OMP_MAX_TERMS 16
+#define SL_OMP_MIN_PIVOT 1e-10
+#define SL_OMP_RESIDUAL_DONE 1e-8
+int sl_omp_init(const float* d_x, int64_t C, int64_t D, int64_t s, int64_t* d_ids, double* d_coefs, float* d_corr,
+                double* d_explained, int32_t* d_n_terms, int32_t* d_finished, float* d_residual, float* d_last, void* stream);
+int sl_omp_step(const float* d_x, int64_t C, int64_t D, const float* d_w, int64_t V, const float* d_cand_vals,
+                const int64_t* d_cand_ids, int64_t k_cand, int64_t t, int64_t s, double min_correlation, int64_t* d_ids,
+                double* d_chol, double* d_rhs, double* d_coefs, float* d_corr, double* d_explained, int32_t* d_n_terms,
+                int32_t* d_finished, float* d_residual, float* d_last, void* stream);
+
 /* normalize(x) @ normalize(y)^T for ANY shapes — x (M,K), y (N,K), out (M,N) — with K6's kernels and arithmetic mode
  * (sl_set_gemm_mode) and none of similarity_score's shape branches: what the tiled top-k probing calls per tile.
  * d_ws: sl_cosine_nt_ws_bytes(M,N,K) bytes. */
@@ -658,7 +699,7 @@ size_t sl_cosine_nt_ws_bytes(int64_t M, int64_t N, int64_t K);
 #define SL_PROF_GATHER 3
 #define SL_PROF_SCORES 4
 #define SL_PROF_BATCHNORM 5 /* K16 fused inference BatchNorm; launches = BatchNorm2d evaluations (K19) */
-#define SL_PROF_TOPK 6 /* K17 streaming fp32 top-k; K20 mutual best matches; K22 per-segment maxima; K24 redundancy groups; K26 ranks */
+#define SL_PROF_TOPK 6 /* K17 streaming fp32 top-k; K20 mutual best matches; K22 per-segment maxima; K24 redundancy groups; K26 ranks; K28 pursuit steps */
 #define SL_PROF_SOFTMAX 7 /* K25 streaming softmax statistics */
 #define SL_PROF_NFAM 8
 int sl_prof_enable(int on);

@@ -141,6 +141,9 @@ SIGNATURES = {
     "sl_softmax_finish": (_int, [_vp, _i64, ctypes.c_double, _vp, _i64, _vp, _vp, _vp, _vp]),
     "sl_rank_merge": (_int, [_vp, _i64, _i64, _vp, _i64, _i64, _i64, _vp, _vp, _vp]),
     "sl_rank_merge_splits": (_i64, [_i64, _i64]),
+    "sl_omp_init": (_int, [_vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "sl_omp_step": (_int, [_vp, _i64, _i64, _vp, _i64, _vp, _vp, _i64, _i64, _i64, ctypes.c_double, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                           _vp, _vp, _vp, _vp]),
     "sl_mutualmax_merge": (_int, [_vp, _vp, _i64, _i64, _vp, _i64, _i64, _i64, _vp]),
     "sl_mutualmax_finish": (_int, [_vp, _i64, _vp, _vp, _vp]),
     "sl_segmax_merge": (_int, [_vp, _i64, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _vp]),
@@ -1262,6 +1265,123 @@ def rank_probe(x: torch.Tensor, y: torch.Tensor, key_vals: torch.Tensor, key_ids
         return counts, folds
 
     return _row_probe("rank_probe", x, y, chunk_rows, setup)
+
+
+# ------------------------------------------------------------------------------------------------
+# K28: orthogonal matching pursuit over a vocabulary — K6 + K17 find the candidates of a pass, one kernel does the step between two
+# ------------------------------------------------------------------------------------------------
+OMP_MAX_TERMS = 16  # include/semanticlens_amd.h: SL_OMP_MAX_TERMS
+OMP_MIN_PIVOT = 1e-10  # SL_OMP_MIN_PIVOT and SL_OMP_RESIDUAL_DONE: design constants (csrc/omp_state.hpp says what they mean)
+OMP_RESIDUAL_DONE = 1e-8
+
+# What a pursuit carries per component (the header describes every array); ``residual`` is the working row the next pass reads —
+# zeros once the component is finished — and ``last`` the residual to report, complete after step ``s - 1``.
+OmpState = namedtuple("OmpState", "ids chol rhs coefs corr explained n_terms finished residual last")
+
+
+def check_omp_terms(n_terms) -> int:
+    try:
+        if isinstance(n_terms, bool):
+            raise TypeError
+        n_terms = operator.index(n_terms)
+    except TypeError:
+        raise ValueError(f"n_terms must be an integer, got {n_terms!r}") from None
+    if not 1 <= n_terms <= OMP_MAX_TERMS:
+        raise ValueError(f"n_terms = {n_terms} not in [1, {OMP_MAX_TERMS}]")
+    return n_terms
+
+
+def check_min_correlation(min_correlation) -> float:
+    try:
+        if isinstance(min_correlation, (str, bytes, bool)):
+            raise TypeError
+        value = float(min_correlation)
+    except (TypeError, ValueError):
+        raise ValueError(f"min_correlation must be a number, got {min_correlation!r}") from None
+    if not (math.isfinite(value) and 0.0 <= value < 1.0):
+        raise ValueError(f"min_correlation = {value} must be finite and in [0, 1)")
+    return value
+
+
+def _check_omp_rows(what: str, name: str, t: torch.Tensor, cols: int | None = None):
+    if t.ndim != 2 or t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous() or (cols is not None and t.shape[1] != cols):
+        width = "D" if cols is None else str(cols)
+        raise ValueError(f"{what}: {name} must be a contiguous (n, {width}) float32 device tensor, got {tuple(t.shape)} {t.dtype} on "
+                         f"{t.device}")
+
+
+def omp_new(x: torch.Tensor, s: int) -> OmpState:
+    """The empty state of a pursuit of ``s`` terms for the components ``x (C, D)`` (contiguous fp32 on the device): ``x / |x|`` as the
+    working residual, no term chosen; a zero row or one with a non-finite coordinate is finished at once (``explained`` and
+    ``last`` NaN)."""
+    s = check_omp_terms(s)
+    _check_omp_rows("omp_new", "the components", x)
+    C, D = x.shape
+    dev = x.device
+    st = OmpState(ids=torch.empty((C, s), dtype=torch.int64, device=dev),
+                  chol=torch.empty((C, s * (s + 1) // 2), dtype=torch.float64, device=dev),
+                  rhs=torch.empty((C, s), dtype=torch.float64, device=dev),
+                  coefs=torch.empty((C, s), dtype=torch.float64, device=dev),
+                  corr=torch.empty((C, s), dtype=torch.float32, device=dev),
+                  explained=torch.empty((C, s), dtype=torch.float64, device=dev),
+                  n_terms=torch.empty((C,), dtype=torch.int32, device=dev),
+                  finished=torch.empty((C,), dtype=torch.int32, device=dev),
+                  residual=torch.empty((C, D), dtype=torch.float32, device=dev),
+                  last=torch.empty((C, D), dtype=torch.float32, device=dev))
+    with _on(dev):
+        rc = lib().sl_omp_init(_ptr(x), C, D, s, _ptr(st.ids), _ptr(st.coefs), _ptr(st.corr), _ptr(st.explained), _ptr(st.n_terms),
+                               _ptr(st.finished), _ptr(st.residual), _ptr(st.last), _stream(x))
+    _check(rc, "sl_omp_init")
+    return st
+
+
+def omp_step(state: OmpState, x: torch.Tensor, w: torch.Tensor, cand_vals: torch.Tensor, cand_ids: torch.Tensor, t: int,
+             min_correlation: float = 0.0):
+    """Step ``t`` of the pursuit (K28, one launch): per unfinished component take the first of the candidates
+    ``(cand_vals, cand_ids) (C, k >= t + 1)`` — best first, ids indexing the rows of ``w (V, D)`` — that is not chosen yet, append it,
+    solve the least squares and write the new residual, or stop the component (``csrc/omp_state.hpp`` holds the rules).  ``x`` and
+    ``w`` are contiguous fp32 device tensors and are used where they lie: any 4-byte aligned start works."""
+    s = state.ids.shape[1]
+    _check_omp_rows("omp_step", "the components", x)
+    C, D = x.shape
+    _check_omp_rows("omp_step", "the vocabulary", w, D)
+    if (cand_vals.shape != cand_ids.shape or cand_vals.ndim != 2 or cand_vals.shape[0] != C or cand_vals.dtype != torch.float32
+            or cand_ids.dtype != torch.int64 or cand_vals.device != x.device or cand_ids.device != x.device):
+        raise ValueError(f"omp_step: candidates must be (C = {C}, k) float32 values and int64 ids on {x.device}, got "
+                         f"{tuple(cand_vals.shape)} {cand_vals.dtype} / {tuple(cand_ids.shape)} {cand_ids.dtype}")
+    shapes = dict(ids=(C, s), chol=(C, s * (s + 1) // 2), rhs=(C, s), coefs=(C, s), corr=(C, s), explained=(C, s), n_terms=(C,),
+                  finished=(C,), residual=(C, D), last=(C, D))
+    for name, shape in shapes.items():
+        part = getattr(state, name)
+        if tuple(part.shape) != shape or part.device != x.device or not part.is_contiguous():
+            raise ValueError(f"omp_step: state.{name} {tuple(part.shape)} on {part.device} is not a contiguous {shape} tensor on {x.device}")
+    cand_vals, cand_ids = cand_vals.contiguous(), cand_ids.contiguous()
+    with _on(x.device):
+        rc = lib().sl_omp_step(_ptr(x), C, D, _ptr(w), w.shape[0], _ptr(cand_vals), _ptr(cand_ids), cand_vals.shape[1], t, s,
+                               min_correlation, _ptr(state.ids), _ptr(state.chol), _ptr(state.rhs), _ptr(state.coefs),
+                               _ptr(state.corr), _ptr(state.explained), _ptr(state.n_terms), _ptr(state.finished),
+                               _ptr(state.residual), _ptr(state.last), _stream(x))
+    _check(rc, "sl_omp_step")
+
+
+def decompose_probe(x: torch.Tensor, w: torch.Tensor, s: int, min_correlation: float = 0.0, chunk_rows: int | None = None) -> OmpState:
+    """Greedy orthogonal matching pursuit of every row of ``x (C, D)`` over the rows of ``w (V, D)``, ``s`` terms at most: the final
+    ``OmpState``.  Step ``t`` is one ``topk_probe`` of the working residuals with ``k = t + 1`` — among ``t + 1`` candidates one is not
+    chosen yet — then one ``omp_step``, all on one stream; the ``(C, V)`` matrix is never formed and nothing is read back."""
+    s = check_omp_terms(s)
+    min_correlation = check_min_correlation(min_correlation)
+    _check_probe_args("decompose_probe", x, w, chunk_rows=chunk_rows)
+    if w.shape[0] == 0:
+        raise ValueError("decompose_probe: the vocabulary is empty")
+    xd = _f32c(x)
+    wd = _f32c(w, xd.device)
+    state = omp_new(xd, s)
+    if xd.shape[0] == 0:
+        return state
+    for t in range(s):
+        vals, ids = topk_probe(state.residual, wd, t + 1, chunk_rows)
+        omp_step(state, xd, wd, vals, ids, t, min_correlation)
+    return state
 
 # ------------------------------------------------------------------------------------------------
 # K20: mutual best matches (row and column maxima of every cosine tile in one read)

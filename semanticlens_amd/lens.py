@@ -562,6 +562,120 @@ def label_rank(fm, vocabulary: list[str], aggregated_concept_db, targets, templa
     return out if is_dict else out[None]
 
 
+# ------------------------------------------------------------------------------------------------
+# describe, jointly: which few words TOGETHER span a component (matching pursuit: K6 + K17 per pass, K28 between)
+# ------------------------------------------------------------------------------------------------
+@dataclass
+class Decomposition:
+    """What ``decompose_components`` / ``probe_decompose`` return for one layer: per component a sparse sum of words,
+    ``x / |x| = sum_t coefs[t] * w[ids[t]] / |w[ids[t]]| + residual``, found greedily (orthogonal matching pursuit) with ``s`` terms
+    at most.
+
+    * ``ids (C, s)`` int64: the vocabulary index of term ``t``, in the order chosen; -1 in an unused slot.
+    * ``coefs (C, s)`` float64: the least-squares weights of the unit-norm word vectors for the unit-norm component, solved over
+      ALL chosen words (so they are the weights of the final set, not those at the moment of choice); 0.0 unused.
+    * ``correlation (C, s)`` float32: the cosine between the residual and the word at the moment it was chosen; NaN unused.
+    * ``explained (C, s)`` float64: ``1 - |residual|^2`` after ``t + 1`` terms, cumulative and non-decreasing; an unused slot repeats
+      the last value (0.0 for a component without any term).
+    * ``n_terms (C,)`` int32: terms used.  A component stops early when no unchosen word has a cosine above ``min_correlation``, when
+      the best one depends linearly on the chosen ones (a duplicate vocabulary entry), or when ``|residual|^2 <= 1e-8``.
+    * ``residual (C, D)`` float32: what the chosen words do not span, in units of the normalised component.
+
+    A component that is a zero row or has a non-finite coordinate has ``n_terms`` 0, ``explained`` and ``residual`` NaN."""
+
+    ids: torch.Tensor
+    coefs: torch.Tensor
+    correlation: torch.Tensor
+    explained: torch.Tensor
+    n_terms: torch.Tensor
+    residual: torch.Tensor
+
+    def terms(self, c: int, vocabulary) -> list:
+        """``[(word, coef, explained)]`` of component ``c``, in the order the words were chosen."""
+        n = int(self.n_terms[c])
+        ids, coefs, explained = self.ids[c, :n].tolist(), self.coefs[c, :n].tolist(), self.explained[c, :n].tolist()
+        return [(vocabulary[i], a, e) for i, a, e in zip(ids, coefs, explained)]
+
+
+def _check_decompose_args(n_terms, min_correlation, chunk_rows=None):
+    n_terms = N.check_omp_terms(n_terms)
+    min_correlation = N.check_min_correlation(min_correlation)
+    if chunk_rows is not None and chunk_rows < 1:
+        raise ValueError(f"chunk_rows = {chunk_rows} must be at least 1")
+    return n_terms, min_correlation
+
+
+def _decompose_layers(names, layers, is_dict, vocab_embeds: torch.Tensor, n_terms: int, min_correlation: float, chunk_rows):
+    """``N.decompose_probe`` per layer against ONE resident vocabulary (moved only when a layer lives on another device, checked
+    finite once per device); results on the device each layer came from."""
+    out, w = {}, None
+    for name, layer in zip(names, layers):
+        db = N._f32c(layer)
+        if w is None or w.device != db.device:
+            w = N._f32c(vocab_embeds, db.device)
+            if not bool(torch.isfinite(w).all()):
+                raise ValueError("the vocabulary embeddings hold a NaN or an infinite value")
+        st = N.decompose_probe(db, w, n_terms, min_correlation, chunk_rows)
+        dev = layer.device
+        out[name] = Decomposition(st.ids.to(dev), st.coefs.to(dev), st.corr.to(dev), st.explained.to(dev), st.n_terms.to(dev),
+                                  st.last.to(dev))
+    return out if is_dict else out[None]
+
+
+@torch.no_grad()
+def probe_decompose(vocab_embeds: torch.Tensor, aggregated_concept_db, n_terms: int = 4, min_correlation: float = 0.0,
+                    chunk_rows: int | None = None):
+    """Decompose every component of a concept DB (a ``(C, D)`` tensor or a dict of layers) into a sparse sum of the rows of
+    ``vocab_embeds (V, D)``, for callers who bring their own vectors: a ``Decomposition`` (a dict of them for a dict DB).
+
+    Greedy orthogonal matching pursuit.  With ``r_0 = x / |x|`` and nothing chosen, step ``t`` of ``n_terms`` (1 to 16): the cosine
+    GEMM (K6) and the streaming top-k (K17, ``k = t + 1``) give every residual's best words without the ``(C, V)`` matrix; one kernel
+    (K28) takes per component the best word not chosen yet, stops the component if its cosine is NaN or ``<= min_correlation`` (finite,
+    in ``[0, 1)``) or if the word depends linearly on the chosen ones, and otherwise solves the least squares over all chosen words in
+    float64 and writes the new residual, recomputed from ``x``.  Cosines are signed: a word is chosen for pointing along the residual,
+    not against it.  ``vocab_embeds`` must be finite (``ValueError``); ``V x D x 4`` bytes of it stay on the device throughout.
+    ``chunk_rows``: as in ``probe_topk``.  Arguments are checked before a device is touched."""
+    n_terms, min_correlation = _check_decompose_args(n_terms, min_correlation, chunk_rows)
+    names, layers, is_dict = _db_layers(aggregated_concept_db)
+    if not isinstance(vocab_embeds, torch.Tensor):
+        raise ValueError(f"vocab_embeds must be a (V, D) tensor, got {type(vocab_embeds).__name__}")
+    _check_width(vocab_embeds, layers)
+    if vocab_embeds.shape[0] == 0:
+        raise ValueError("vocab_embeds holds no rows")
+    return _decompose_layers(names, layers, is_dict, vocab_embeds, n_terms, min_correlation, chunk_rows)
+
+
+@torch.no_grad()
+def decompose_components(fm, vocabulary: list[str], aggregated_concept_db, n_terms: int = 4, templates: list[str] | None = None,
+                         batch_size: int | None = None, chunk_size: int | None = None, min_correlation: float = 0.0,
+                         chunk_rows: int | None = None):
+    """For every component, the few words of ``vocabulary`` that TOGETHER span its embedding, with weights and the share left
+    unexplained: a ``Decomposition`` for a ``(C, D)`` tensor, a dict of them for a dict of layers (for a ``Facets``, pass
+    ``facets.aggregated()``), on the DB's device.  Where ``label_components`` scores every word on its own — so the five best labels
+    of a component with two meanings are five synonyms of the dominant one — the pursuit removes what the chosen words explain
+    before it looks for the next (``probe_decompose`` states the algorithm).
+
+    The vocabulary is embedded once, ``chunk_size`` words at a time exactly as ``label_components`` embeds it (templates included),
+    into ONE resident ``(V, D)`` fp32 device tensor: the pursuit revisits the whole vocabulary ``n_terms`` times and re-reads the rows
+    it chose, so ``V x D x 4`` bytes must fit on the device (410 MB for 100 000 words of width 1 024) — unlike ``label_components``,
+    which never holds more than a chunk.  ``n_terms``, ``min_correlation``, ``chunk_rows``, the vocabulary, ``chunk_size`` and the DB's
+    shape are checked before the text tower or a device is touched; a ``D`` mismatch can only raise once the first chunk is embedded."""
+    n_terms, min_correlation = _check_decompose_args(n_terms, min_correlation, chunk_rows)
+    if isinstance(vocabulary, str) or not isinstance(vocabulary, (list, tuple)) or len(vocabulary) == 0:
+        raise ValueError("vocabulary must be a non-empty list of strings")
+    vocabulary = list(vocabulary)
+    names, layers, is_dict = _db_layers(aggregated_concept_db)
+    chunks = _embedded_chunks(fm, vocabulary, layers, templates, batch_size, chunk_size)
+    if layers:
+        N._f32c(layers[0][:0])  # raises without a HIP device, before the text tower runs
+    w = None
+    for start, stop, embeds in chunks:
+        if w is None:
+            w = torch.empty((len(vocabulary), embeds.shape[1]), dtype=torch.float32, device=N.to_device(embeds).device)
+        w[start:stop] = embeds
+    return _decompose_layers(names, layers, is_dict, w, n_terms, min_correlation, chunk_rows)
+
+
 @torch.no_grad()
 def search_components(fm, query, aggregated_concept_db, k: int = 10, templates: list[str] | None = None,
                       batch_size: int | None = None):
@@ -976,6 +1090,11 @@ class Lens:
 
     def label_rank(self, vocabulary, aggregated_concept_db, targets, templates=None, batch_size=None, chunk_size=None, logit_scale=None):
         return label_rank(self.fm, vocabulary, aggregated_concept_db, targets, templates, batch_size, chunk_size, logit_scale)
+
+    def decompose_components(self, vocabulary, aggregated_concept_db, n_terms=4, templates=None, batch_size=None, chunk_size=None,
+                             min_correlation=0.0, chunk_rows=None):
+        return decompose_components(self.fm, vocabulary, aggregated_concept_db, n_terms, templates, batch_size, chunk_size,
+                                    min_correlation, chunk_rows)
 
     def search_components(self, query, aggregated_concept_db, k=10, templates=None, batch_size=None):
         return search_components(self.fm, query, aggregated_concept_db, k, templates, batch_size)
