@@ -545,6 +545,16 @@ int sl_topk_init(float* d_vals, int64_t* d_ids, int64_t R, int64_t k, void* stre
 int sl_topk_merge(float* d_vals, int64_t* d_ids, int64_t R, int64_t k, const float* d_cand, int64_t ld, int64_t B,
                   int64_t id_base, void* d_ws, size_t ws_bytes, void* stream);
 size_t sl_topk_merge_ws_bytes(int64_t R, int64_t k, int64_t B);
+/* K29: K17's fold of a candidate tile, ranking column j of row r by
+ * biased_score(cand[r][j], d_row_bias[r], d_col_bias[j]) = (2 cand - row bias) - column bias in fp32 (csrc/biased_score.hpp; CSLS,
+ * the hubness correction behind label_components_csls) instead of by cand[r][j]; the state holds SCORES.  d_row_bias (R,),
+ * d_col_bias (B,: the tile's first column is d_col_bias[0]), any 4-byte alignment.  NaN and infinities follow IEEE arithmetic
+ * (inf - inf = NaN) and a NaN score ranks first.  Everything else — state layout, sl_topk_init, empty slots, id_base, ld,
+ * k <= 1024, split rows and workspace, tiling invariance — is sl_topk_merge's.  A state built by it is merged with
+ * sl_topk_merge_states unchanged. */
+int sl_topk_merge_biased(float* d_vals, int64_t* d_ids, int64_t R, int64_t k, const float* d_cand, int64_t ld, int64_t B,
+                         int64_t id_base, const float* d_row_bias, const float* d_col_bias, void* d_ws, size_t ws_bytes, void* stream);
+/* workspace: sl_topk_merge_ws_bytes(R, k, B) */
 /* Fold M explicit entries per row — d_other_vals / d_other_ids (R,M), e.g. another state (M = k) or the states of several
  * layers or ranks side by side — into the state.  Entries with a negative id are empty slots; the caller keeps ids distinct. */
 int sl_topk_merge_states(float* d_vals, int64_t* d_ids, int64_t R, int64_t k, const float* d_other_vals,

@@ -9,9 +9,10 @@ HIP device, compute calls raise.
 from __future__ import annotations
 
 from semanticlens_amd import foundation_models, scores, utils
-from semanticlens_amd.lens import (ConceptAudit, ConceptDBComparison, Decomposition, LabelDistribution, LabelRanks, Lens,
-                                   audit_concepts, compare_concept_dbs, decompose_components, label_distribution, label_facets,
-                                   label_rank, probe_decompose, probe_rank, probe_setmax, probe_softmax, search_facets)
+from semanticlens_amd.lens import (ConceptAudit, ConceptDBComparison, Decomposition, HubnessLabels, LabelDistribution, LabelRanks, Lens,
+                                   audit_concepts, compare_concept_dbs, decompose_components, label_components_csls,
+                                   label_distribution, label_facets, label_rank, probe_csls, probe_decompose, probe_rank,
+                                   probe_setmax, probe_softmax, search_facets)
 from semanticlens_amd.scores import (Facets, RedundancyGroups, clarity_score, polysemanticity_facets, polysemanticity_score,
                                      redundancy_groups, redundancy_score, silhouette_samples, silhouette_score)
 
@@ -36,6 +37,9 @@ __all__ = [
     "decompose_components",
     "Decomposition",
     "probe_decompose",
+    "label_components_csls",
+    "HubnessLabels",
+    "probe_csls",
     "clarity_score",
     "polysemanticity_score",
     "redundancy_score",

@@ -133,6 +133,7 @@ SIGNATURES = {
                                                  ctypes.c_double, _i64, _i64, _vp, _vp]),
     "sl_topk_init": (_int, [_vp, _vp, _i64, _i64, _vp]),
     "sl_topk_merge": (_int, [_vp, _vp, _i64, _i64, _vp, _i64, _i64, _i64, _vp, _sz, _vp]),
+    "sl_topk_merge_biased": (_int, [_vp, _vp, _i64, _i64, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _sz, _vp]),
     "sl_topk_merge_ws_bytes": (_sz, [_i64, _i64, _i64]),
     "sl_topk_merge_states": (_int, [_vp, _vp, _i64, _i64, _vp, _vp, _i64, _vp]),
     "sl_softmax_init": (_int, [_vp, _i64, _vp]),
@@ -914,6 +915,27 @@ def topk_merge(vals: torch.Tensor, ids: torch.Tensor, cand: torch.Tensor, id_bas
     _check(rc, "sl_topk_merge")
 
 
+def topk_merge_biased(vals: torch.Tensor, ids: torch.Tensor, cand: torch.Tensor, row_bias: torch.Tensor, col_bias: torch.Tensor,
+                      id_base: int = 0, ws: torch.Tensor | None = None):
+    """``topk_merge`` under another score (K29): column ``j`` of row ``r`` ranks by ``(2 * cand[r, j] - row_bias[r]) - col_bias[j]``
+    in fp32 (csrc/biased_score.hpp) and the state holds the scores.  ``row_bias (R,)`` and ``col_bias (B,)``: contiguous float32 on
+    the tile's device; ``col_bias[0]`` belongs to the tile's first column, whatever ``id_base``."""
+    R, k = vals.shape
+    _check_cand_tile("topk_merge_biased", cand, rows=R)
+    B = cand.shape[1]
+    for name, bias, n in (("row_bias", row_bias, R), ("col_bias", col_bias, B)):
+        if bias.ndim != 1 or bias.dtype != torch.float32 or bias.shape[0] != n or bias.device != cand.device or not bias.is_contiguous():
+            raise ValueError(f"topk_merge_biased: {name} must be a contiguous 1-D float32 tensor of {n} entries on {cand.device}, got "
+                             f"{tuple(bias.shape)} {bias.dtype} on {bias.device}")
+    cand, ld = _tile_view(cand)
+    nbytes = int(lib().sl_topk_merge_ws_bytes(R, k, B))
+    ws = _ws_for(nbytes, ws, vals.device)
+    with _on(vals.device):
+        rc = lib().sl_topk_merge_biased(_ptr(vals), _ptr(ids), R, k, _ptr(cand), ld, B, id_base, _ptr(row_bias), _ptr(col_bias), _ptr(ws),
+                                        nbytes, _stream(vals))
+    _check(rc, "sl_topk_merge_biased")
+
+
 def topk_merge_states(vals: torch.Tensor, ids: torch.Tensor, other_vals: torch.Tensor, other_ids: torch.Tensor):
     """Fold ``(R, M)`` explicit (value, id) entries into the state (negative ids are empty slots)."""
     R, k = vals.shape
@@ -1041,6 +1063,56 @@ def topk_probe(x: torch.Tensor, y: torch.Tensor, k: int, chunk_rows: int | None 
         return (vals, ids), [_topk_fold(vals, ids, id_base)]
 
     return _row_probe("topk_probe", x, y, chunk_rows, setup)
+
+
+# ------------------------------------------------------------------------------------------------
+# K29: hubness-corrected (CSLS) top-k over the same cosine tiles
+# ------------------------------------------------------------------------------------------------
+def check_neighbours(m) -> int:
+    """The neighbourhood size of a CSLS density: an integer in ``[1, TOPK_MAX_K]`` (a density is the mean of a K17 state's row)."""
+    try:
+        m = operator.index(m)
+    except TypeError:
+        raise ValueError(f"neighbours must be an integer, got {m!r}") from None
+    if m < 1 or m > TOPK_MAX_K:
+        raise ValueError(f"neighbours = {m} not in [1, {TOPK_MAX_K}]")
+    return m
+
+
+def topk_density(vals: torch.Tensor, ids: torch.Tensor) -> torch.Tensor:
+    """``(R,)`` float32: per row of a K17 state the mean, taken in float64, of the entries present (``ids >= 0``); NaN for a row
+    without any.  Plain torch on the state's device: the state is ``(R, m)``, not a hot path."""
+    present = ids >= 0
+    total = torch.where(present, vals.to(torch.float64), 0.0).sum(1)
+    return (total / present.sum(1)).to(torch.float32)
+
+
+def csls_probe(x: torch.Tensor, y: torch.Tensor, k: int, neighbours: int = 10, chunk_rows: int | None = None):
+    """Per row of ``x (R, D)``: the ``k`` rows of ``y (N, D)`` of largest CSLS score (Conneau et al. 2018),
+    ``csls(i, j) = 2 cos(x_i, y_j) - r_i - q_j``, as ``(scores (R, k) float32, ids (R, k) int64, r (R,) float32, q (N,) float32)``.
+    ``r_i`` is the mean of row ``i``'s ``neighbours`` largest cosines over ``y`` (how crowded its neighbourhood is), ``q_j`` the mean
+    of ``y_j``'s ``neighbours`` largest cosines over ``x`` (how much of a hub ``y_j`` is); with fewer candidates than ``neighbours``
+    on a side, the mean over those present.
+
+    Three passes over the ``_row_probe`` walk, none of which forms the ``(R, N)`` matrix: ``topk_probe(x, y)`` gives ``r``,
+    ``topk_probe(y, x)`` gives ``q``, and in the third K29 folds each cosine tile ranking it by the score, computed in registers
+    (csrc/biased_score.hpp) from the tile, ``r`` and the tile's slice of ``q``.  Order: K17's on the score, NaN first; a NaN
+    cosine or density makes the score NaN.  An empty ``x`` or ``y`` gives K17's empty result and empty or NaN densities."""
+    k = check_topk_k(k)
+    m = check_neighbours(neighbours)
+    _check_probe_args("csls_probe", x, y, chunk_rows=chunk_rows)
+    xd = _f32c(x)
+    yd = _f32c(y, xd.device)
+    r = topk_density(*topk_probe(xd, yd, m, chunk_rows))
+    q = topk_density(*topk_probe(yd, xd, m, chunk_rows))
+
+    def setup(R, device):
+        vals, ids = topk_new(R, k, device)
+        fold = _Fold(lambda R, step: lib().sl_topk_merge_ws_bytes(R, k, step),
+                     lambda out, c0, ws: topk_merge_biased(vals, ids, out, r, q[c0 : c0 + out.shape[1]], c0, ws))
+        return (vals, ids, r, q), [fold]
+
+    return _row_probe("csls_probe", xd, yd, chunk_rows, setup)
 
 
 # ------------------------------------------------------------------------------------------------

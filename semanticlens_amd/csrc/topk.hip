@@ -18,6 +18,12 @@
 // Few rows (search: a handful of queries against tens of thousands of components): the columns are split over S waves per
 // row, each of which selects its segment's top k into a workspace (filtered by the state's k-th entry: what that rejects
 // cannot reach the result), and a second launch folds the S lists into the state with the explicit-id kernel.
+//
+// K29 (sl_topk_merge_biased) is the same fold of the same tile under another score: column j of row r ranks by
+// biased_score(cand[r][j], row_bias[r], col_bias[j]) (biased_score.hpp), computed in registers from the chunk the wave holds and
+// the chunk's 16 column biases per lane, so no adjusted tile is ever written.  The state then holds scores; the threshold test,
+// the LDS selection, the split rows and the list fold do not know the difference.
+#include "biased_score.hpp"
 #include "packed_best.hpp"  // f32_order_key
 #include "rowseg_tile.hpp"
 
@@ -116,11 +122,31 @@ __host__ __device__ inline int pow2_entries(int k) {
   return n;
 }
 
+// The column biases of piece u of the chunk at column `base`, laid out as rowseg::load_chunk lays out the tile's: columns
+// [base + (u * 64 + lane) * 4, + 4), 0 where a column is outside [lo, hi) (nothing outside the segment is read).  colb + base lies
+// on a 16-byte boundary only when the caller's slice of the bias vector happens to start where the row does, so a whole piece is
+// copied as 16 bytes of 4-byte alignment (gfx950 runs with unaligned global access enabled; preprocess.hip: load12): one
+// global_load_dwordx4 either way.
+__device__ inline f4 load_bias_piece(const float* __restrict__ colb, int64_t base, int u, int64_t lo, int64_t hi, int lane) {
+  const int64_t c = base + (int64_t)(u * kWave + lane) * 4;
+  f4 q;
+  if (c >= lo && c + 4 <= hi) {
+    __builtin_memcpy(&q, colb + c, 16);
+  } else {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) q[j] = (c + j >= lo && c + j < hi) ? colb[c + j] : 0.f;
+  }
+  return q;
+}
+
 // One wave per (row, split).  S == 1: fold columns [0,B) of the row into the state in place.  S > 1: select the top k of
 // columns [s*seg, (s+1)*seg) into list s of the row in the workspace (wv / wid: (R, S, k)).
+// kBiased (K29): the candidates are biased_score(cand, rowb[row], colb[column]); rowb and colb are not looked at otherwise.
+template <bool kBiased>
 __global__ __launch_bounds__(64) void topk_tile_kernel(float* __restrict__ vals, int64_t* __restrict__ ids, int64_t R, int k,
                                                          const float* __restrict__ cand, int64_t ld, int64_t B, int64_t id_base,
-                                                         int S, int64_t seg, float* __restrict__ wv, int64_t* __restrict__ wid) {
+                                                         int S, int64_t seg, float* __restrict__ wv, int64_t* __restrict__ wid,
+                                                         const float* __restrict__ rowb, const float* __restrict__ colb) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int lane = threadIdx.x;
   WaveTopK st;
@@ -141,13 +167,23 @@ __global__ __launch_bounds__(64) void topk_tile_kernel(float* __restrict__ vals,
     }
     bool touched = false;
     const float* rowp = cand + row * ld;
+    float rb = 0.f;
+    if constexpr (kBiased) rb = rowb[row];
     for (int64_t base = rowseg::chunk_start((uintptr_t)(rowp + lo), lo); base < hi; base += rowseg::kChunk) {
       f4 x[4];
       rowseg::load_chunk(rowp, base, lo, hi, lane, 0.f, x);
+      if constexpr (kBiased) {
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+          const f4 q = load_bias_piece(colb, base, u, lo, hi, lane);
+#pragma unroll
+          for (int j = 0; j < 4; ++j) x[u][j] = biased_score(x[u][j], rb, q[j]);
+        }
+      }
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
-        // the common case: no key in these 256 columns reaches the k-th entry's (columns outside [lo,hi) read as 0.0 and are
-        // sorted out below)
+        // the common case: no key in these 256 columns reaches the k-th entry's (columns outside [lo,hi) read as 0.0, or as the
+        // score of a zero cosine under a zero column bias, and are sorted out below whatever that is)
         bool any = false;
 #pragma unroll
         for (int j = 0; j < 4; ++j) any = any || f32_order_key(x[u][j]) >= st.tk;
@@ -248,34 +284,56 @@ SL_API size_t sl_topk_merge_ws_bytes(int64_t R, int64_t k, int64_t B) {
   return S > 1 ? (size_t)R * (size_t)S * (size_t)k * 12 + 256 : 0;
 }
 
-SL_API int sl_topk_merge(float* d_vals, int64_t* d_ids, int64_t R, int64_t k, const float* d_cand, int64_t ld, int64_t B,
-                         int64_t id_base, void* d_ws, size_t ws_bytes, void* stream) {
-  if (int rc = check_state("sl_topk_merge", R, k)) return rc;
-  if (int rc = rowseg::check_tile_shape("sl_topk_merge", B, ld)) return rc;
-  SL_REQUIRE(id_base >= 0 && id_base <= kMaxId - B, "sl_topk_merge: ids from id_base = %lld leave [0, 2^62]", (long long)id_base);
+namespace {
+
+// sl_topk_merge (kBiased false, no bias vectors) and sl_topk_merge_biased: one order of refusals, one launch
+template <bool kBiased>
+int merge_tile(const char* fn, float* d_vals, int64_t* d_ids, int64_t R, int64_t k, const float* d_cand, int64_t ld, int64_t B,
+               int64_t id_base, const float* d_row_bias, const float* d_col_bias, void* d_ws, size_t ws_bytes, void* stream) {
+  if (int rc = check_state(fn, R, k)) return rc;
+  if (int rc = rowseg::check_tile_shape(fn, B, ld)) return rc;
+  SL_REQUIRE(id_base >= 0 && id_base <= kMaxId - B, "%s: ids from id_base = %lld leave [0, 2^62]", fn, (long long)id_base);
   if (R == 0) return 0;
-  SL_REQUIRE(d_vals && d_ids, "sl_topk_merge: null state");
-  if (int rc = rowseg::check_tile_ptr("sl_topk_merge", d_cand)) return rc;
+  SL_REQUIRE(d_vals && d_ids, "%s: null state", fn);
+  if (int rc = rowseg::check_tile_ptr(fn, d_cand)) return rc;
+  if constexpr (kBiased) {
+    SL_REQUIRE(d_row_bias && d_col_bias, "%s: null bias vector", fn);
+    SL_REQUIRE((((uintptr_t)d_row_bias | (uintptr_t)d_col_bias) & 3) == 0, "%s: a bias vector is not 4-byte aligned", fn);
+  }
   const int64_t S = rowseg::splits(R, B, num_cus());
   hipStream_t st = (hipStream_t)stream;
   ProfScope prof(SL_PROF_TOPK, st, (double)R * (double)B * 4);
   if (S == 1) {
-    SL_LAUNCH(prof, topk_tile_kernel, dim3((unsigned)wave_grid(R, k)), dim3(64), lds_bytes(k), st, d_vals, d_ids, R, (int)k, d_cand,
-              ld, B, id_base, 1, B, (float*)nullptr, (int64_t*)nullptr);
+    SL_LAUNCH(prof, topk_tile_kernel<kBiased>, dim3((unsigned)wave_grid(R, k)), dim3(64), lds_bytes(k), st, d_vals, d_ids, R, (int)k,
+              d_cand, ld, B, id_base, 1, B, (float*)nullptr, (int64_t*)nullptr, d_row_bias, d_col_bias);
     SL_CHECK_HIP(hipGetLastError());
     return 0;
   }
-  SL_REQUIRE(d_ws && ws_bytes >= sl_topk_merge_ws_bytes(R, k, B), "sl_topk_merge: workspace too small");
+  SL_REQUIRE(d_ws && ws_bytes >= sl_topk_merge_ws_bytes(R, k, B), "%s: workspace too small", fn);
   int64_t* wid = (int64_t*)rowseg::align_ws(d_ws);
   float* wv = (float*)(wid + R * S * k);
   const int64_t seg = rowseg::segment(B, S);
-  SL_LAUNCH(prof, topk_tile_kernel, dim3((unsigned)wave_grid(R * S, k)), dim3(64), lds_bytes(k), st, d_vals, d_ids, R, (int)k,
-            d_cand, ld, B, id_base, (int)S, seg, wv, wid);
+  SL_LAUNCH(prof, topk_tile_kernel<kBiased>, dim3((unsigned)wave_grid(R * S, k)), dim3(64), lds_bytes(k), st, d_vals, d_ids, R,
+            (int)k, d_cand, ld, B, id_base, (int)S, seg, wv, wid, d_row_bias, d_col_bias);
   ProfScope fold(SL_PROF_TOPK, st, (double)R * (double)S * (double)k * 12);
   SL_LAUNCH(fold, topk_lists_kernel, dim3((unsigned)wave_grid(R, k)), dim3(64), lds_bytes(k), st, d_vals, d_ids, R, (int)k, wv, wid,
             S * k);
   SL_CHECK_HIP(hipGetLastError());
   return 0;
+}
+
+}  // namespace
+
+SL_API int sl_topk_merge(float* d_vals, int64_t* d_ids, int64_t R, int64_t k, const float* d_cand, int64_t ld, int64_t B,
+                         int64_t id_base, void* d_ws, size_t ws_bytes, void* stream) {
+  return merge_tile<false>("sl_topk_merge", d_vals, d_ids, R, k, d_cand, ld, B, id_base, nullptr, nullptr, d_ws, ws_bytes, stream);
+}
+
+SL_API int sl_topk_merge_biased(float* d_vals, int64_t* d_ids, int64_t R, int64_t k, const float* d_cand, int64_t ld, int64_t B,
+                                int64_t id_base, const float* d_row_bias, const float* d_col_bias, void* d_ws, size_t ws_bytes,
+                                void* stream) {
+  return merge_tile<true>("sl_topk_merge_biased", d_vals, d_ids, R, k, d_cand, ld, B, id_base, d_row_bias, d_col_bias, d_ws, ws_bytes,
+                          stream);
 }
 
 SL_API int sl_topk_merge_states(float* d_vals, int64_t* d_ids, int64_t R, int64_t k, const float* d_other_vals,

@@ -201,6 +201,22 @@ def _embedded_chunks(fm, texts: list[str], layers, templates: list[str] | None, 
     return chunks()
 
 
+def _embed_vocabulary(fm, vocabulary: list[str], layers, templates: list[str] | None, batch_size: int | None,
+                      chunk_size: int | None) -> torch.Tensor:
+    """The whole vocabulary as ONE resident ``(V, D)`` fp32 device tensor, embedded ``chunk_size`` words at a time exactly as
+    ``label_components`` embeds it (``_embedded_chunks``: ``chunk_size`` is checked by the call, before the text tower runs).  For
+    the callers that revisit every word after having seen them all (``decompose_components``, ``label_components_csls``)."""
+    chunks = _embedded_chunks(fm, vocabulary, layers, templates, batch_size, chunk_size)
+    if layers:
+        N._f32c(layers[0][:0])  # raises without a HIP device, before the text tower runs
+    w = None
+    for start, stop, embeds in chunks:
+        if w is None:
+            w = torch.empty((len(vocabulary), embeds.shape[1]), dtype=torch.float32, device=N.to_device(embeds).device)
+        w[start:stop] = embeds
+    return w
+
+
 def _probe_layers(names, layers, is_dict, query_embeds: torch.Tensor, probe):
     """``probe(layer, queries) -> (values, ids)`` per layer, both operands on the layer's device as contiguous fp32 (the queries
     move only when the device changes); results on the device the layer came from, a dict of them for a dict DB."""
@@ -372,6 +388,116 @@ def label_distribution(fm, vocabulary: list[str], aggregated_concept_db, k: int 
         tensors = (vals, ids, *N.softmax_finish(sm, scale, vals))
         out[name] = LabelDistribution(*(t.to(layer.device) for t in tensors), n_labels=len(vocabulary), logit_scale=scale)
     return out if is_dict else out[None]
+
+
+# ------------------------------------------------------------------------------------------------
+# describe, without the hubs: labels ranked by CSLS, not by the raw cosine (K6 + K17 twice for the densities, K29)
+# ------------------------------------------------------------------------------------------------
+@dataclass
+class HubnessLabels:
+    """What ``label_components_csls`` / ``probe_csls`` return for one layer: per component its ``k`` best labels under the CSLS
+    score ``2 cos(x_i, w_j) - r_i - q_j`` (Conneau et al. 2018), which discounts a cosine by how crowded both ends' neighbourhoods are.
+
+    * ``values (C, k)`` float32: the scores, best first (K17's order on the score: NaN first, larger first, ties by the smaller
+      id); ``-inf`` in an unused slot (``k`` beyond the vocabulary).
+    * ``ids (C, k)`` int64: index the vocabulary; ``-1`` unused.
+    * ``component_density (C,)`` float32: ``r``, the mean of the component's ``neighbours`` largest cosines over the vocabulary.
+    * ``label_density (V,)`` float32: ``q``, the mean of the word's ``neighbours`` largest cosines over THIS layer's components: how
+      much of a hub the word is here.
+    * ``neighbours``: the neighbourhood size; with fewer candidates on a side the density is the mean over those present."""
+
+    values: torch.Tensor
+    ids: torch.Tensor
+    component_density: torch.Tensor
+    label_density: torch.Tensor
+    neighbours: int
+
+    @property
+    def cosine(self) -> torch.Tensor:
+        """``(C, k)`` float32: the cosine of each returned pair, recovered as ``float32((float64(score) + r_i + q_id) / 2)`` — within
+        1.5e-7 of the cosine the score was taken from; NaN in an unused slot."""
+        present = self.ids >= 0
+        q = self.label_density.to(torch.float64)[self.ids.clamp(min=0)] if self.label_density.numel() else 0.0
+        cos = (self.values.to(torch.float64) + self.component_density.to(torch.float64)[:, None] + q) / 2
+        return torch.where(present, cos, float("nan")).to(torch.float32)
+
+    def hubs(self, n: int = 20):
+        """``(values, ids)`` of the ``n`` words of largest ``label_density``, largest first (a NaN density before every number, equal
+        densities by the smaller id): the hubs themselves, worth printing once per layer."""
+        n = operator.index(n)
+        if n < 0:
+            raise ValueError(f"n = {n} must not be negative")
+        vals, ids = torch.sort(self.label_density, descending=True, stable=True)
+        return vals[:n], ids[:n]
+
+
+def _check_csls_args(k, neighbours, chunk_rows=None):
+    k, neighbours = N.check_topk_k(k), N.check_neighbours(neighbours)
+    if chunk_rows is not None and chunk_rows < 1:
+        raise ValueError(f"chunk_rows = {chunk_rows} must be at least 1")
+    return k, neighbours
+
+
+def _csls_layers(names, layers, is_dict, vocab_embeds: torch.Tensor, k: int, neighbours: int, chunk_rows):
+    """``N.csls_probe`` per layer against ONE resident vocabulary (moved only when a layer lives on another device); each layer has
+    its own label densities; results on the device each layer came from."""
+    out, w = {}, None
+    for name, layer in zip(names, layers):
+        db = N._f32c(layer)
+        if w is None or w.device != db.device:
+            w = N._f32c(vocab_embeds, db.device)
+        vals, ids, r, q = N.csls_probe(db, w, k, neighbours, chunk_rows)
+        out[name] = HubnessLabels(*(t.to(layer.device) for t in (vals, ids, r, q)), neighbours=neighbours)
+    return out if is_dict else out[None]
+
+
+@torch.no_grad()
+def probe_csls(vocab_embeds: torch.Tensor, aggregated_concept_db, k: int = 5, neighbours: int = 10, chunk_rows: int | None = None):
+    """``probe_topk(per="component")`` ranked by CSLS instead of the raw cosine, for callers who bring their own vectors: a
+    ``HubnessLabels`` for a ``(C, D)`` tensor, a dict of them for a dict of layers.
+
+    ``csls(i, j) = 2 cos(x_i, w_j) - r_i - q_j`` with ``r_i`` the mean of component ``i``'s ``neighbours`` (1 to 1 024) largest cosines
+    over ``vocab_embeds (V, D)`` and ``q_j`` the mean of word ``j``'s ``neighbours`` largest cosines over the layer's components.  A
+    word that is close to every component (a hub: "photo", a template's residue) has a large ``q`` and loses its lead to the word
+    that is close to this component only.  Three passes of the cosine GEMM (K6) per layer, none of which forms the ``(C, V)``
+    matrix: K17 over components x words gives ``r``, K17 over words x components gives ``q``, and K29 folds the tiles of the third
+    ranking them by the score, computed in registers.  ``V x D x 4`` bytes of ``vocab_embeds`` stay on the device throughout.
+
+    A NaN cosine or density makes the score NaN, and a NaN ranks first, as in ``label_components``.  ``chunk_rows``: as in
+    ``probe_topk``.  Arguments are checked before a device is touched."""
+    k, neighbours = _check_csls_args(k, neighbours, chunk_rows)
+    names, layers, is_dict = _db_layers(aggregated_concept_db)
+    if not isinstance(vocab_embeds, torch.Tensor):
+        raise ValueError(f"vocab_embeds must be a (V, D) tensor, got {type(vocab_embeds).__name__}")
+    _check_width(vocab_embeds, layers)
+    if vocab_embeds.shape[0] == 0:
+        raise ValueError("vocab_embeds holds no rows")
+    return _csls_layers(names, layers, is_dict, vocab_embeds, k, neighbours, chunk_rows)
+
+
+@torch.no_grad()
+def label_components_csls(fm, vocabulary: list[str], aggregated_concept_db, k: int = 5, neighbours: int = 10,
+                          templates: list[str] | None = None, batch_size: int | None = None, chunk_size: int | None = None,
+                          chunk_rows: int | None = None):
+    """``label_components`` with the hubs discounted: for every component its ``k`` best labels out of ``vocabulary`` under the CSLS
+    score (``probe_csls`` states it), as a ``HubnessLabels`` for a ``(C, D)`` tensor, a dict of them for a dict of layers (for a
+    ``Facets``, pass ``facets.aggregated()``), on the DB's device.  Raw cosines sit on a large common offset, and the few words that
+    lie near it head the top-5 of most components; here they are scored down by their own density (``hl.hubs()`` lists them) and the
+    word that tells a component apart comes first.  Each layer is independent: ``label_density`` is taken over that layer's components.
+
+    The vocabulary is embedded once, ``chunk_size`` words at a time exactly as ``label_components`` embeds it (templates included),
+    into ONE resident ``(V, D)`` fp32 device tensor: both densities need the whole vocabulary before the scoring pass can start, so
+    ``V x D x 4`` bytes must fit on the device (410 MB for 100 000 words of width 1 024) — unlike ``label_components``, which never
+    holds more than a chunk.  A NaN cosine or density makes the score NaN, and a NaN ranks first, as in ``label_components``.
+    ``k``, ``neighbours``, ``chunk_rows``, the vocabulary, ``chunk_size`` and the DB's shape are checked before the text tower or a device
+    is touched; a ``D`` mismatch can only raise once the first chunk is embedded."""
+    k, neighbours = _check_csls_args(k, neighbours, chunk_rows)
+    if isinstance(vocabulary, str) or not isinstance(vocabulary, (list, tuple)) or len(vocabulary) == 0:
+        raise ValueError("vocabulary must be a non-empty list of strings")
+    vocabulary = list(vocabulary)
+    names, layers, is_dict = _db_layers(aggregated_concept_db)
+    w = _embed_vocabulary(fm, vocabulary, layers, templates, batch_size, chunk_size)
+    return _csls_layers(names, layers, is_dict, w, k, neighbours, chunk_rows)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -665,14 +791,7 @@ def decompose_components(fm, vocabulary: list[str], aggregated_concept_db, n_ter
         raise ValueError("vocabulary must be a non-empty list of strings")
     vocabulary = list(vocabulary)
     names, layers, is_dict = _db_layers(aggregated_concept_db)
-    chunks = _embedded_chunks(fm, vocabulary, layers, templates, batch_size, chunk_size)
-    if layers:
-        N._f32c(layers[0][:0])  # raises without a HIP device, before the text tower runs
-    w = None
-    for start, stop, embeds in chunks:
-        if w is None:
-            w = torch.empty((len(vocabulary), embeds.shape[1]), dtype=torch.float32, device=N.to_device(embeds).device)
-        w[start:stop] = embeds
+    w = _embed_vocabulary(fm, vocabulary, layers, templates, batch_size, chunk_size)
     return _decompose_layers(names, layers, is_dict, w, n_terms, min_correlation, chunk_rows)
 
 
@@ -1095,6 +1214,11 @@ class Lens:
                              min_correlation=0.0, chunk_rows=None):
         return decompose_components(self.fm, vocabulary, aggregated_concept_db, n_terms, templates, batch_size, chunk_size,
                                     min_correlation, chunk_rows)
+
+    def label_components_csls(self, vocabulary, aggregated_concept_db, k=5, neighbours=10, templates=None, batch_size=None,
+                              chunk_size=None, chunk_rows=None):
+        return label_components_csls(self.fm, vocabulary, aggregated_concept_db, k, neighbours, templates, batch_size, chunk_size,
+                                     chunk_rows)
 
     def search_components(self, query, aggregated_concept_db, k=10, templates=None, batch_size=None):
         return search_components(self.fm, query, aggregated_concept_db, k, templates, batch_size)
